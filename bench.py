@@ -16,6 +16,11 @@ torch.distributed never touches RCCL here: every data-path collective is issued 
 
 Prints ONE JSON line on rank 0.  `value` = (voxels filled + samples ray-marched) per second over the whole job,
 in millions; the two halves are also reported separately.
+
+A plain run does what the headline needs: set-up, warm-up, the timed steps, the line.  `--full` adds what is measured beside it, all
+untimed: the formula sample count of SURVEY 8(d) (one ray-march before the warm-up), the content variants and the CPU baseline (after the
+timed region).  `--dump-outputs DIR` writes the frame of the last timed step (the image a caller of vp_raymarch receives) as DIR/image.npy;
+the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -39,6 +44,7 @@ load_package()
 from vpfx_amd import abi, engine as E, scene as S  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s achievable
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs budget: a larger image is written as a fixed, seeded sample of its pixels
 
 
 def baseline_metric():
@@ -141,6 +147,21 @@ def cpu_baseline(sc, threads=0, boxes=None):
     return out
 
 
+def dump_outputs(out_dir, image):
+    """Write the frame of the last timed step (height x width x RGBA, float32) as out_dir/image.npy.  Above DUMP_MAX_BYTES (the 4K screens
+    of config 5) it is image_sample.npy instead: the RGBA of a fixed, seeded set of pixels (row-major pixel indices, ascending), the same
+    pixels in every run of the same config."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = image.cpu().numpy().astype(np.float32, copy=False)
+    if img.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+        return
+    px = img.reshape(-1, img.shape[-1])
+    n = DUMP_MAX_BYTES // 2 // px[0].nbytes
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), np.ascontiguousarray(px[idx]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -166,7 +187,17 @@ def main():
     ap.add_argument("--no-reference-frame", action="store_true", help="N > 1: do not render the 1-GPU frame on rank 0 for the shard check")
     ap.add_argument("--no-variants", action="store_true",
                     help="skip the untimed content variants after the timed region (float cube map, coloured ambient, +x view: `variants` in the JSON line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the formula sample count, the content variants and the CPU baseline "
+                         "(each can still be left out with its --no-* switch); a plain run skips all three")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/image.npy (float32, height x width x RGBA; rank 0); frames over 64 MB "
+                         "as DIR/image_sample.npy, a fixed, seeded sample of their pixels")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_formula_count = args.no_variants = args.no_cpu_baseline = True
     # TEST HOOKS (tests/test_gpu_bench_cli.py runs the DRIVER'S command line byte for byte on a one-GPU box, so the switches cannot be flags):
     #   VPFX_BENCH_SHARE_GPU=1        = --share-gpu
     #   VPFX_BENCH_TEST_FAIL_RANK=r   rank r dies (os._exit) in the middle of the timed region: the job must exit non-zero, not hang
@@ -331,6 +362,8 @@ def main():
                 k_fin.append(eng.last_kernel_ms(3))
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, image)          # before the variants below draw into the same image
     st = eng.stats()
     info = eng.multi_info()
     t = torch.tensor([dt], dtype=torch.float64)

@@ -28,7 +28,7 @@ def _bench(*args):
 
 
 def test_single_gpu_line_has_roofline_and_cpu_baseline():
-    d = _bench()
+    d = _bench("--full")
     assert d["n_gpus"] == 1 and d["config"]["launch"] == "single GPU" and d["config"]["rccl_ranks"] is None
     rf = d["roofline"]
     assert rf["bound"] == "hbm" and rf["peak"] == 8000.0 and 0 < rf["frac"] < 1 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-12
@@ -42,6 +42,18 @@ def test_single_gpu_line_has_roofline_and_cpu_baseline():
         assert x["fill_ms"] > 0 and x["raymarch_ms"] > 0 and x["ms_per_step"] >= x["fill_ms"] + x["raymarch_ms"], name
     assert v["coloured_ambient"]["brick_format"] == "RGBA16F" and v["cubemap_f32"]["brick_format"] == "grey z-pair"
     assert d["config"]["brick_storage"].startswith("grey")           # the headline's own storage is untouched by the variants
+
+
+def test_plain_line_measures_the_headline_only_and_dumps_the_last_frame(tmp_path):
+    """Without --full: no CPU baseline, no content variants, no formula-count launch; --dump-outputs writes the last timed frame."""
+    import numpy as np
+    d = _bench("--dump-outputs", str(tmp_path))
+    assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["value"] > 0 and d["roofline"]["frac"] > 0
+    assert "cpu_baseline" not in d and d["variants"] is None and d["config"]["samples_formula"] is None
+    img = np.load(tmp_path / "image.npy")
+    w, h = (int(x) for x in d["config"]["workload"].rsplit(", ", 1)[1].split("x"))
+    assert img.dtype == np.float32 and img.shape == (h, w, 4) and np.isfinite(img).all()
+    assert img.std() > 0                                           # particles in view: not a blank frame
 
 
 @pytest.mark.parametrize("n,exchange", [(2, "tiles"), (4, "all_gather")])
