@@ -38,7 +38,9 @@ extern "C" {
                                    VP_MULTI_TEST_HOOKS / VP_MULTI_TEST_DROP_SEND, VP_RM_NO_EARLY_OUT, vp_exchange_plan, vp_unity_clear_slot, vp_unity_register_output_fd
                                 5: same struct layouts; new: the particle source (vp_emitter_*)
                                 6: same struct layouts; new: vp_occluder / vp_set_occluders2 (cylinder and ellipsoid occluders beside boxes).
-                                   Stricter since 5: vp_emitter_config.reserved[] must be 0 and .lifetime finite, <= 1e5 s (VP_ERR_BAD_ARG otherwise) */
+                                   Stricter since 5: vp_emitter_config.reserved[] must be 0 and .lifetime finite, <= 1e5 s (VP_ERR_BAD_ARG otherwise)
+                                6 (additive): mesh occluders -- vp_mesh / vp_mesh_instance, vp_set_occluder_meshes / vp_set_occluder_instances; no
+                                   existing layout or entry point changed: a host detects the feature by the presence of the symbols */
 
 typedef enum vp_status {
     VP_OK = 0,
@@ -337,6 +339,43 @@ int  vp_set_occluders(vp_ctx* ctx, const vp_obb* boxes, int32_t n);
  * solids; light depth map: vp_set_frame's arguments, the solids and light_near / light_far / light_cam_distance); passing a map of your own
  * replaces it. */
 int  vp_set_occluders2(vp_ctx* ctx, const vp_occluder* solids, int32_t n);
+/* ABI 6 (additive): triangle-mesh occluders beside the solids -- any opaque mesh on the Default layer (VPR.cs:184 cullingMask), drawn into both
+ * depth inputs the way Unity rasterises it, without reading Unity's depth textures back.
+ *   vp_mesh           one shape in object space (Unity Mesh.vertices / Mesh.triangles).  Unity winding: Cross(b - a, c - a) points out of the
+ *                     front face.
+ *   vp_mesh_instance  one placed copy: object_to_world = Renderer.localToWorldMatrix (column-major like every matrix of the ABI, affine: the last
+ *                     row must be 0 0 0 1), mesh = index into the list of the last vp_set_occluder_meshes, reserved[] = 0.
+ * Semantics:
+ *   - same rays as the solids: pixel-centre rays with the origin / direction / depth of vp_render_light_depth and vp_render_scene_depth.  The
+ *     light map stores (t - near) / (far - near), cleared 1; the eye map linear eye depth, cleared 3e38; hits outside [near, far] are dropped.
+ *   - culling as the reference draws: under the light camera a triangle counts only where it faces AWAY from the light (the nearest back face,
+ *     LDM.shader:6 Cull Front); under the main camera only where it faces the camera (Cull Back, Unity's opaque default).  The outward normal
+ *     is sign(det(M3x3)) * Cross(Mb - Ma, Mc - Ma): a mirrored instance culls the way Unity draws it.  The test is watertight (a ray through
+ *     a shared edge or vertex of a closed mesh is never let through between its triangles).
+ *   - solids and mesh instances are combined per texel / pixel by a minimum; with no instances every map is what the solids alone give.
+ *   - an instance whose 3x3 part has determinant 0 adds nothing; zero-area triangles add nothing.
+ *   - VP_ERR_BAD_ARG: an index outside [0, n_vertices), a non-finite vertex or matrix entry, a non-affine matrix, mesh out of range, non-zero
+ *     reserved[], n < 0, a null array with n > 0, n_vertices / n_triangles < 0 or null arrays behind non-zero counts.  More than 2^24
+ *     instanced triangles in total (VP_MESH_MAX_TRIANGLES), or more than 2^31 - 1 vertices / indices over the shape list, is VP_ERR_UNSUPPORTED.
+ *     A refused call leaves the previous state in effect.
+ *   - vp_set_occluder_meshes replaces the shape list and removes every placed instance (they name shapes by index); n = 0 clears both.
+ *     vp_set_occluder_instances replaces the placed instances; n = 0 removes them.  Both invalidate the kept maps (see vp_set_occluders2);
+ *     a caller-supplied light_depth_map / scene_depth still overrides everything.
+ *   - rendering a map with instances set costs one host wait (the size of the per-tile triangle lists is read back); a frame whose tile
+ *     lists would exceed 2^28 entries is VP_ERR_UNSUPPORTED.  Without instances nothing of this runs. */
+#define VP_MESH_MAX_TRIANGLES 16777216
+typedef struct vp_mesh {
+    const float*   positions;     /* [n_vertices][3]                                               */
+    const int32_t* indices;       /* [n_triangles][3]                                              */
+    int32_t        n_vertices, n_triangles;
+} vp_mesh;                        /* 24 bytes on LP64 */
+typedef struct vp_mesh_instance {
+    float   object_to_world[16];  /* Renderer.localToWorldMatrix, column-major, affine             */
+    int32_t mesh;                 /* index into the shape list                                     */
+    int32_t reserved[3];          /* must be 0                                                     */
+} vp_mesh_instance;               /* 80 bytes */
+int  vp_set_occluder_meshes(vp_ctx* ctx, const vp_mesh* meshes, int32_t n);
+int  vp_set_occluder_instances(vp_ctx* ctx, const vp_mesh_instance* instances, int32_t n);
 /* Parity probes: render and read back the two maps. */
 int  vp_render_light_depth(vp_ctx* ctx, float light_near, float light_far, float light_cam_distance, float* out /* [(Ny*nv)][(Nx*nv)] */);
 int  vp_render_scene_depth(vp_ctx* ctx, const vp_camera* cam, float* out /* [H][W] linear eye depth, 3e38 = nothing */);

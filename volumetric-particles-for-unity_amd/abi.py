@@ -182,6 +182,19 @@ def as_occluders(solids):
     return arr
 
 
+VP_MESH_MAX_TRIANGLES = 1 << 24      # instanced triangles over all placed mesh instances
+
+
+class vp_mesh(C.Structure):
+    """ABI 6 (additive): one occluder shape in object space (Unity Mesh.vertices / Mesh.triangles)."""
+    _fields_ = [("positions", C.c_void_p), ("indices", C.c_void_p), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32)]
+
+
+class vp_mesh_instance(C.Structure):
+    """ABI 6 (additive): one placed occluder shape (object_to_world column-major, affine; reserved = 0)."""
+    _fields_ = [("object_to_world", C.c_float * 16), ("mesh", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class vp_emitter_config(C.Structure):
     """Parameters of the library's particle source (the demo scene's ParticleSystem, scene:2264-2620)."""
     _fields_ = [("seed", C.c_uint64), ("rate", C.c_float), ("lifetime", C.c_float), ("speed", C.c_float), ("size", C.c_float),
@@ -228,7 +241,7 @@ EXPORTED_SYMBOLS = [
     "vp_raymarch", "vp_raymarch_device", "vp_raymarch_async", "vp_wait_image", "vp_clear_particles_rt", "vp_render_metavoxel", "vp_read_particles_rt", "vp_composite_device",
     "vp_fill_local", "vp_fill_finish", "vp_fill_finish_gathered", "vp_raymarch_partial_device", "vp_blend_partials_device",
     "vp_blend_partials_range_device",
-    "vp_z_boundary", "vp_z_histogram", "vp_set_occluders", "vp_set_occluders2", "vp_render_light_depth", "vp_render_scene_depth",
+    "vp_z_boundary", "vp_z_histogram", "vp_set_occluders", "vp_set_occluders2", "vp_set_occluder_meshes", "vp_set_occluder_instances", "vp_render_light_depth", "vp_render_scene_depth",
     "vp_get_mv_positions", "vp_read_binlist", "vp_read_bincounts", "vp_read_brick",
     "vp_read_lightmap", "vp_get_stats", "vp_last_kernel_ms",
     "vp_raymarch_partial_handoff_device", "vp_read_zsamples",

@@ -55,8 +55,12 @@ namespace MetavoxelEngine
             SceneMeshes,         // every enabled MeshRenderer on the Default layer (lightCamera.cullingMask, VPR.cs:346) whose mesh is Unity's
                                  // Cube / Cylinder / Sphere goes to the library as an analytic solid (vp_set_occluders2); the library renders
                                  // BOTH depth inputs on the GPU -- nothing is read back from Unity.  The reference's scene is 4 cubes + 4 cylinders
-            UnityDepthTextures   // the reference's own way: lightCamera.RenderWithShader (VPR.cs:184) and the main camera's depth texture
+            UnityDepthTextures,  // the reference's own way: lightCamera.RenderWithShader (VPR.cs:184) and the main camera's depth texture
                                  // (VPR.cs:152, 204), both read back through `copyDepthMaterial` and passed as pointers
+            AllSceneMeshes       // SceneMeshes' primitives as analytic solids, and EVERY other Default-layer MeshFilter as a triangle mesh
+                                 // (vp_set_occluder_meshes once per distinct sharedMesh set, vp_set_occluder_instances with each renderer's
+                                 // localToWorldMatrix when something moved): any mesh shadows the volume and rejects samples, nothing is read back.
+                                 // The meshes must be readable (Read/Write enabled in the import settings)
         }
         public OccluderSource occluderSource = OccluderSource.SceneMeshes;
         public Material copyDepthMaterial;         // UnityDepthTextures: csharp/VpfxCopyDepth.shader (pass 0: raw depth, pass 1: linear eye depth)
@@ -117,6 +121,21 @@ namespace MetavoxelEngine
         }
 
         [StructLayout(LayoutKind.Sequential)]
+        struct vp_mesh                         // ABI 6 (additive): one occluder shape in object space; IntPtr fields over pinned arrays
+        {
+            public IntPtr positions, indices;  // float[n_vertices * 3], int[n_triangles * 3] (Mesh.vertices / Mesh.triangles)
+            public int n_vertices, n_triangles;
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
+        struct vp_mesh_instance                // ABI 6 (additive): one renderer placing a shape (80 bytes)
+        {
+            [MarshalAs(UnmanagedType.ByValArray, SizeConst = 16)] public float[] object_to_world;
+            public int mesh;
+            [MarshalAs(UnmanagedType.ByValArray, SizeConst = 3)] public int[] reserved;
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
         struct vp_unity_frame                  // one frame for the render-thread callback (include/vpfx.h "Unity native-plugin hookup")
         {
             public IntPtr ctx; public int flags, particle_count;
@@ -147,6 +166,8 @@ namespace MetavoxelEngine
         [DllImport(LIB)] static extern int vp_unpin_host_buffer(IntPtr ctx, IntPtr ptr);
         [DllImport(LIB)] static extern int vp_rebalance(IntPtr ctx);
         [DllImport(LIB)] static extern int vp_set_occluders2(IntPtr ctx, IntPtr solids, int n);   // IntPtr: an array of vp_occluder marshalled by hand (ByValArray members)
+        [DllImport(LIB)] static extern int vp_set_occluder_meshes(IntPtr ctx, vp_mesh[] meshes, int n);
+        [DllImport(LIB)] static extern int vp_set_occluder_instances(IntPtr ctx, IntPtr instances, int n);   // IntPtr: vp_mesh_instance[] marshalled by hand
         [DllImport(LIB)] static extern IntPtr vp_unity_render_event_func();
         [DllImport(LIB)] static extern int vp_unity_set_frame_desc(int slot, ref vp_unity_frame frame);
         [DllImport(LIB)] static extern int vp_unity_register_output(int slot, IntPtr dRgbaOut, IntPtr hRgbaOut);
@@ -173,6 +194,7 @@ namespace MetavoxelEngine
         GCHandle lightDepthHandle, sceneDepthHandle;
         Texture2D lightDepthTex, sceneDepthTex;
         int occluderHash = 0; bool occludersSent = false;
+        int meshShapesHash = 0; bool meshShapesSent = false;   // AllSceneMeshes: the sharedMesh list the context holds
 
         static float[] ToArray(Matrix4x4 m)   // Unity Matrix4x4 is column-major in memory: m00,m10,m20,m30,m01,...
         {
@@ -325,6 +347,8 @@ namespace MetavoxelEngine
             if (occluderSource == OccluderSource.None) return;
             if (occluderSource == OccluderSource.UnityDepthTextures) { ReadBackDepthTextures(); return; }
             var solids = new List<vp_occluder>();
+            var shapes = new List<Mesh>();
+            var instances = new List<vp_mesh_instance>();
             int hash = 17;
             int defaultLayer = LayerMask.NameToLayer("Default");
             foreach (MeshRenderer mr in FindObjectsOfType<MeshRenderer>())
@@ -335,7 +359,16 @@ namespace MetavoxelEngine
                 int type;
                 string mesh = mf.sharedMesh.name;
                 if (mesh == "Cube") type = 0; else if (mesh == "Cylinder") type = 1; else if (mesh == "Sphere") type = 2;
-                else continue;                                             // other meshes: use OccluderSource.UnityDepthTextures
+                else if (occluderSource == OccluderSource.AllSceneMeshes)
+                {
+                    int shape = shapes.IndexOf(mf.sharedMesh);
+                    if (shape < 0) { shape = shapes.Count; shapes.Add(mf.sharedMesh); }
+                    Matrix4x4 l2w = mr.localToWorldMatrix;
+                    instances.Add(new vp_mesh_instance { object_to_world = ToArray(l2w), mesh = shape, reserved = new int[3] });
+                    hash = hash * 31 + l2w.GetHashCode(); hash = hash * 31 + mf.sharedMesh.GetInstanceID();
+                    continue;
+                }
+                else continue;                                             // other meshes (SceneMeshes): use OccluderSource.AllSceneMeshes or UnityDepthTextures
                 Transform t = mr.transform;
                 Vector3 c = t.position, sc = t.lossyScale, ax = t.right, ay = t.up, az = t.forward;
                 // Unity's primitives: Cube spans [-0.5, 0.5]^3; Cylinder: radius 0.5, height 2 about local y; Sphere: radius 0.5
@@ -350,7 +383,48 @@ namespace MetavoxelEngine
             try
             {
                 for (int i = 0; i < solids.Count; i++) Marshal.StructureToPtr(solids[i], new IntPtr(buf.ToInt64() + (long)i * size), false);
-                if (Check(vp_set_occluders2(ctx, solids.Count > 0 ? buf : IntPtr.Zero, solids.Count), "vp_set_occluders2")) { occluderHash = hash; occludersSent = true; }
+                bool ok = Check(vp_set_occluders2(ctx, solids.Count > 0 ? buf : IntPtr.Zero, solids.Count), "vp_set_occluders2");
+                if (occluderSource == OccluderSource.AllSceneMeshes) ok = SyncOccluderMeshes(shapes, instances) && ok;
+                if (ok) { occluderHash = hash; occludersSent = true; }
+            }
+            finally { Marshal.FreeHGlobal(buf); }
+        }
+
+        // AllSceneMeshes: the shapes (vertex data) only when the set of distinct sharedMeshes changed, the 80-byte instances whenever something moved.
+        // The library copies during each call, so the pins end with it.
+        bool SyncOccluderMeshes(List<Mesh> shapes, List<vp_mesh_instance> instances)
+        {
+            int shapesHash = 17;
+            foreach (Mesh m in shapes) shapesHash = shapesHash * 31 + m.GetInstanceID();
+            if (!meshShapesSent || shapesHash != meshShapesHash)
+            {
+                var pins = new List<GCHandle>();
+                var descs = new vp_mesh[Math.Max(1, shapes.Count)];
+                try
+                {
+                    for (int i = 0; i < shapes.Count; i++)
+                    {
+                        Vector3[] v = shapes[i].vertices;
+                        int[] tri = shapes[i].triangles;
+                        var pos = new float[v.Length * 3];
+                        for (int k = 0; k < v.Length; k++) { pos[3 * k] = v[k].x; pos[3 * k + 1] = v[k].y; pos[3 * k + 2] = v[k].z; }
+                        GCHandle hp = GCHandle.Alloc(pos, GCHandleType.Pinned);
+                        pins.Add(hp);
+                        GCHandle ht = GCHandle.Alloc(tri, GCHandleType.Pinned);
+                        pins.Add(ht);
+                        descs[i] = new vp_mesh { positions = hp.AddrOfPinnedObject(), indices = ht.AddrOfPinnedObject(), n_vertices = v.Length, n_triangles = tri.Length / 3 };
+                    }
+                    if (!Check(vp_set_occluder_meshes(ctx, descs, shapes.Count), "vp_set_occluder_meshes")) return false;
+                    meshShapesHash = shapesHash; meshShapesSent = true;
+                }
+                finally { foreach (GCHandle h in pins) h.Free(); }
+            }
+            int size = Marshal.SizeOf(typeof(vp_mesh_instance));            // 80
+            IntPtr buf = Marshal.AllocHGlobal(Math.Max(1, instances.Count) * size);
+            try
+            {
+                for (int i = 0; i < instances.Count; i++) Marshal.StructureToPtr(instances[i], new IntPtr(buf.ToInt64() + (long)i * size), false);
+                return Check(vp_set_occluder_instances(ctx, instances.Count > 0 ? buf : IntPtr.Zero, instances.Count), "vp_set_occluder_instances");
             }
             finally { Marshal.FreeHGlobal(buf); }
         }

@@ -1,5 +1,6 @@
 // api.cpp -- the C ABI of include/vpfx.h: argument checking, device-memory ownership, stage sequencing.
 // No compute happens on the host beyond the per-frame uniforms of host_logic.cpp; there is no CPU fallback.
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -143,12 +144,14 @@ int stage_fill_inputs(vp_ctx* c, const vp_fill_params* p)
         { int rcs = stream_sync(c); if (rcs) return rcs; }
         c->have_depthmap = true;
         c->light_depth_gen = 0;                                 // the buffer holds the caller's map now
-    } else if (c->n_occluders > 0) {
+    } else if (has_occluders(c)) {
         // no map given but occluder solids are set: render the light depth map on the GPU (VPR.cs:184) -- unless the buffer already holds exactly that
         if (!c->d_depthmap) { int rc = dev_alloc(c, &c->d_depthmap, lightmap_elems(c)); if (rc) return rc; c->light_depth_gen = 0; }
         const float planes[3] = {p->light_near, p->light_far, p->light_cam_distance};
         if (c->light_depth_gen != c->occl_gen || c->light_depth_frame != c->frame_gen || memcmp(planes, c->light_depth_planes, sizeof planes) != 0) {
-            int rc = launch_light_depth(c, p->light_near, p->light_far, p->light_cam_distance, c->d_depthmap); if (rc) return rc;
+            int rc = launch_light_depth(c, p->light_near, p->light_far, p->light_cam_distance, c->d_depthmap);
+            if (!rc) rc = launch_mesh_light_depth(c, p->light_near, p->light_far, p->light_cam_distance, c->d_depthmap);
+            if (rc) { c->light_depth_gen = 0; return rc; }
             c->light_depth_gen = c->occl_gen; c->light_depth_frame = c->frame_gen; memcpy(c->light_depth_planes, planes, sizeof planes);
         }
         c->have_depthmap = true;
@@ -164,7 +167,9 @@ int ensure_eye_depth(vp_ctx* c, const vp_camera* cam)
 {
     if (!c->d_scene_depth) { int rc = dev_alloc(c, &c->d_scene_depth, (size_t)c->cfg.width * c->cfg.height); if (rc) return rc; c->eye_depth_gen = 0; }
     if (c->eye_depth_gen == c->occl_gen && memcmp(cam, &c->eye_depth_cam, sizeof *cam) == 0) return VP_OK;
-    int rc = launch_scene_depth(c, cam, c->d_scene_depth); if (rc) return rc;
+    int rc = launch_scene_depth(c, cam, c->d_scene_depth);
+    if (!rc) rc = launch_mesh_scene_depth(c, cam, c->d_scene_depth);
+    if (rc) { c->eye_depth_gen = 0; return rc; }
     c->eye_depth_gen = c->occl_gen; c->eye_depth_cam = *cam;
     return VP_OK;
 }
@@ -191,7 +196,7 @@ int stage_raymarch(vp_ctx* c, const vp_camera* cam, const vp_raymarch_params* rp
         VP_HIP(hipMemcpyAsync(c->d_scene_depth, rp->scene_depth, (size_t)c->cfg.width * c->cfg.height * sizeof(float),
                               hipMemcpyHostToDevice, c->stream));
         c->eye_depth_gen = 0;                                   // the buffer holds the caller's depth now
-    } else if (c->n_occluders > 0) {
+    } else if (has_occluders(c)) {
         // no depth buffer given but occluder solids are set: render the eye depth on the GPU (VPR.cs:204) -- unless the buffer already holds it for this camera
         int rc = ensure_eye_depth(c, cam); if (rc) return rc;
     }
@@ -354,6 +359,7 @@ void vp_destroy_single(vp_ctx* c)
                    c->d_occ_list, c->d_ids_tmp, c->d_ids, c->d_onecol, c->d_work_counter, c->d_ord, c->d_colcount, c->d_chain, c->d_cube_u8, c->d_meta, c->d_scan_totals, c->d_bricks, c->d_dens_ao,
                    c->d_lightmap, c->d_cubequads, c->d_depthmap, c->d_occluders, c->d_mvtrans, c->d_brick_hit, c->d_rank, c->d_tile_order, c->d_tile_curve, c->d_image, c->d_scene_depth, c->d_samples, c->d_zsamples, c->d_cellinfo, c->d_occmask};
     for (void* p : dev) if (p) (void)hipFree(p);
+    mesh_free_all(c);
     if (c->h_chain_err) (void)hipHostFree(c->h_chain_err);
     if (c->h_meta_host) (void)hipHostFree(c->h_meta_host);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
@@ -594,7 +600,7 @@ VP_EXPORT int vp_render_metavoxel(vp_ctx* c, const vp_camera* cam, const vp_raym
         VP_HIP(hipMemcpyAsync(c->d_scene_depth, rp->scene_depth, (size_t)c->cfg.width * c->cfg.height * sizeof(float),
                               hipMemcpyHostToDevice, c->stream));
         c->eye_depth_gen = 0;
-    } else if (c->n_occluders > 0) {
+    } else if (has_occluders(c)) {
         rc = ensure_eye_depth(c, cam); if (rc) return rc;
         keep = c->d_scene_depth;
     } else {
@@ -665,7 +671,7 @@ VP_EXPORT int vp_raymarch_device(vp_ctx* c, const vp_camera* cam, const vp_rayma
     RmConsts k;
     rc = stage_raymarch(c, cam, rp, &k); if (rc) return rc;
     float* keep = c->d_scene_depth;
-    if (!rp->scene_depth && c->n_occluders == 0) c->d_scene_depth = nullptr;
+    if (!rp->scene_depth && !has_occluders(c)) c->d_scene_depth = nullptr;
     rc = launch_raymarch(c, k, (float*)d_rgba_out, nullptr);
     c->d_scene_depth = keep;
     return rc;
@@ -741,7 +747,7 @@ VP_EXPORT int vp_raymarch_partial_handoff_device(vp_ctx* c, const vp_camera* cam
         *phase_mask = (k.z0 <= k.zB ? 1 : 0) | (k.z1 - 1 > k.zB ? 2 : 0);
     }
     float* keep = c->d_scene_depth;
-    if (!rp->scene_depth && c->n_occluders == 0) c->d_scene_depth = nullptr;
+    if (!rp->scene_depth && !has_occluders(c)) c->d_scene_depth = nullptr;
     RmHandoff ho{};
     ho.t_in = n_in > 0 ? (const uint8_t*)d_t_in : nullptr; ho.n_in = n_in; ho.plane = (size_t)c->cfg.width * c->cfg.height;
     ho.t_out0 = (uint8_t*)d_t_out0; ho.t_out1 = (uint8_t*)d_t_out1; ho.zsamples = c->no_zprofile ? nullptr : c->d_zsamples;
@@ -861,6 +867,111 @@ VP_EXPORT int vp_set_occluders(vp_ctx* c, const vp_obb* boxes, int32_t n)
     return rc;
 }
 
+// ---- mesh occluders (ABI 6, additive; kernels: occluder_mesh.hip) ---------------------------------------
+namespace {
+
+// a refused call changes nothing: every new buffer is complete before the old one is freed
+template <typename T>
+int upload_new(vp_ctx* c, T** out, const T* src, size_t n)
+{
+    *out = nullptr;
+    if (n == 0) return VP_OK;
+    if (hipMalloc((void**)out, n * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); *out = nullptr; return vp_fail(c, VP_ERR_OOM, "mesh occluders: device allocation failed"); }
+    hipError_t e = hipMemcpyAsync(*out, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream);
+    hipError_t e2 = hipStreamSynchronize(c->stream);                 // the caller's arrays are not retained
+    if (e != hipSuccess || e2 != hipSuccess) { (void)hipFree(*out); *out = nullptr; return vp_fail(c, VP_ERR_HIP, "mesh occluders: upload failed"); }
+    return VP_OK;
+}
+
+void bump_occl_gen(vp_ctx* c) { if (++c->occl_gen == 0) c->occl_gen = 1; }
+
+}  // namespace
+
+VP_EXPORT int vp_set_occluder_meshes(vp_ctx* c, const vp_mesh* meshes, int32_t n)
+{
+    if (!c) return VP_ERR_BAD_ARG;
+    if (n < 0 || (n > 0 && !meshes)) return vp_fail(c, VP_ERR_BAD_ARG, "vp_set_occluder_meshes: bad argument");
+    size_t nv = 0, nt = 0;
+    for (int i = 0; i < n; ++i) {
+        const vp_mesh& m = meshes[i];
+        if (m.n_vertices < 0 || m.n_triangles < 0 || (m.n_vertices > 0 && !m.positions) || (m.n_triangles > 0 && !m.indices))
+            return vp_fail(c, VP_ERR_BAD_ARG, "vp_set_occluder_meshes: mesh %d: bad counts or null array", i);
+        for (size_t k = 0; k < (size_t)m.n_vertices * 3; ++k)
+            if (!std::isfinite(m.positions[k])) return vp_fail(c, VP_ERR_BAD_ARG, "vp_set_occluder_meshes: mesh %d: non-finite vertex", i);
+        for (size_t k = 0; k < (size_t)m.n_triangles * 3; ++k)
+            if (m.indices[k] < 0 || m.indices[k] >= m.n_vertices) return vp_fail(c, VP_ERR_BAD_ARG, "vp_set_occluder_meshes: mesh %d: index out of range", i);
+        nv += (size_t)m.n_vertices; nt += (size_t)m.n_triangles;
+    }
+    if (nv > (size_t)INT32_MAX || nt * 3 > (size_t)INT32_MAX) return vp_fail(c, VP_ERR_UNSUPPORTED, "vp_set_occluder_meshes: more than 2^31 - 1 vertices / indices");
+    if (c->multi) return multi_set_occluder_meshes(c, meshes, n);
+    int rc = ensure_device(c); if (rc) return rc;
+    std::vector<MeshShape> shapes((size_t)n);
+    std::vector<float> pos; std::vector<int32_t> idx;
+    try { pos.resize(nv * 3); idx.resize(nt * 3); } catch (const std::bad_alloc&) { return vp_fail(c, VP_ERR_OOM, "vp_set_occluder_meshes: out of host memory"); }
+    size_t v0 = 0, t0 = 0;
+    for (int i = 0; i < n; ++i) {
+        const vp_mesh& m = meshes[i];
+        shapes[i] = MeshShape{(int64_t)v0, m.n_vertices, (int64_t)t0, m.n_triangles};
+        if (m.n_vertices) memcpy(&pos[v0 * 3], m.positions, (size_t)m.n_vertices * 3 * sizeof(float));
+        for (size_t k = 0; k < (size_t)m.n_triangles * 3; ++k) idx[t0 * 3 + k] = m.indices[k] + (int32_t)v0;     // rebased to the concatenation
+        v0 += (size_t)m.n_vertices; t0 += (size_t)m.n_triangles;
+    }
+    float* d_pos = nullptr; int32_t* d_idx = nullptr;
+    if ((rc = upload_new(c, &d_pos, pos.data(), pos.size()))) return rc;
+    if ((rc = upload_new(c, &d_idx, idx.data(), idx.size()))) { if (d_pos) (void)hipFree(d_pos); return rc; }
+    if (c->d_mesh_pos) (void)hipFree(c->d_mesh_pos);
+    if (c->d_mesh_idx) (void)hipFree(c->d_mesh_idx);
+    c->d_mesh_pos = d_pos; c->d_mesh_idx = d_idx;
+    c->mesh_shapes.swap(shapes);
+    c->n_mesh_inst = c->n_mesh_inst_placed = 0; c->n_mesh_tris = 0;      // instances name shapes by index: a new list removes them
+    bump_occl_gen(c);
+    return VP_OK;
+}
+
+VP_EXPORT int vp_set_occluder_instances(vp_ctx* c, const vp_mesh_instance* inst, int32_t n)
+{
+    if (!c) return VP_ERR_BAD_ARG;
+    if (n < 0 || (n > 0 && !inst)) return vp_fail(c, VP_ERR_BAD_ARG, "vp_set_occluder_instances: bad argument");
+    vp_ctx* shapes_of = c->multi ? multi_owner_of_slice(c, -2) : c;     // every slab context holds the same list
+    const std::vector<MeshShape>& shapes = shapes_of->mesh_shapes;
+    size_t tris = 0;
+    for (int i = 0; i < n; ++i) {
+        const float* m = inst[i].object_to_world;
+        for (int k = 0; k < 16; ++k)
+            if (!std::isfinite(m[k])) return vp_fail(c, VP_ERR_BAD_ARG, "vp_set_occluder_instances: instance %d: non-finite matrix entry", i);
+        if (m[3] != 0.f || m[7] != 0.f || m[11] != 0.f || m[15] != 1.f) return vp_fail(c, VP_ERR_BAD_ARG, "vp_set_occluder_instances: instance %d: matrix not affine", i);
+        if (inst[i].reserved[0] || inst[i].reserved[1] || inst[i].reserved[2]) return vp_fail(c, VP_ERR_BAD_ARG, "vp_set_occluder_instances: instance %d: reserved must be 0", i);
+        if (inst[i].mesh < 0 || (size_t)inst[i].mesh >= shapes.size()) return vp_fail(c, VP_ERR_BAD_ARG, "vp_set_occluder_instances: instance %d: mesh out of range", i);
+        tris += (size_t)shapes[(size_t)inst[i].mesh].n_triangles;
+    }
+    if (tris > (size_t)VP_MESH_MAX_TRIANGLES) return vp_fail(c, VP_ERR_UNSUPPORTED, "vp_set_occluder_instances: %zu instanced triangles (limit 2^24)", tris);
+    if (c->multi) return multi_set_occluder_instances(c, inst, n);
+    int rc = ensure_device(c); if (rc) return rc;
+    std::vector<MeshInstDev> dev; std::vector<uint32_t> first(1, 0u);
+    for (int i = 0; i < n; ++i) {
+        const float* m = inst[i].object_to_world;                     // column-major: element (r, k) = m[k * 4 + r]
+        const MeshShape& sh = shapes[(size_t)inst[i].mesh];
+        const double det = (double)m[0] * ((double)m[5] * m[10] - (double)m[9] * m[6]) - (double)m[4] * ((double)m[1] * m[10] - (double)m[9] * m[2])
+                         + (double)m[8] * ((double)m[1] * m[6] - (double)m[5] * m[2]);
+        if (det == 0.0 || sh.n_triangles == 0) continue;               // a flattened instance adds nothing
+        MeshInstDev d{};
+        for (int r = 0; r < 3; ++r)
+            for (int k = 0; k < 4; ++k) d.m[r * 4 + k] = m[k * 4 + r];
+        d.first_triangle = (int32_t)sh.first_triangle; d.n_triangles = (int32_t)sh.n_triangles; d.mirrored = det < 0.0 ? 1 : 0;
+        dev.push_back(d);
+        first.push_back(first.back() + (uint32_t)sh.n_triangles);
+    }
+    MeshInstDev* d_inst = nullptr; uint32_t* d_first = nullptr;
+    if ((rc = upload_new(c, &d_inst, dev.data(), dev.size()))) return rc;
+    if ((rc = upload_new(c, &d_first, first.data(), dev.empty() ? 0 : first.size()))) { if (d_inst) (void)hipFree(d_inst); return rc; }
+    if (c->d_mesh_inst) (void)hipFree(c->d_mesh_inst);
+    if (c->d_mesh_inst_first) (void)hipFree(c->d_mesh_inst_first);
+    c->d_mesh_inst = d_inst; c->d_mesh_inst_first = d_first;
+    c->n_mesh_inst = (int)dev.size(); c->n_mesh_inst_placed = n; c->n_mesh_tris = first.back();
+    bump_occl_gen(c);
+    return VP_OK;
+}
+
 VP_EXPORT int vp_render_light_depth(vp_ctx* c, float light_near, float light_far, float light_cam_distance, float* out)
 {
     if (!c) return VP_ERR_BAD_ARG;
@@ -871,6 +982,7 @@ VP_EXPORT int vp_render_light_depth(vp_ctx* c, float light_near, float light_far
     float* d_tmp = nullptr;
     VP_HIP(hipMalloc((void**)&d_tmp, lightmap_elems(c) * sizeof(float)));
     rc = launch_light_depth(c, light_near, light_far, light_cam_distance, d_tmp);
+    if (!rc) rc = launch_mesh_light_depth(c, light_near, light_far, light_cam_distance, d_tmp);
     hipError_t e = hipSuccess;
     if (!rc) e = hipMemcpyAsync(out, d_tmp, lightmap_elems(c) * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     hipError_t e2 = hipStreamSynchronize(c->stream);
@@ -890,6 +1002,7 @@ VP_EXPORT int vp_render_scene_depth(vp_ctx* c, const vp_camera* cam, float* out)
     float* d_tmp = nullptr;
     VP_HIP(hipMalloc((void**)&d_tmp, n * sizeof(float)));
     rc = launch_scene_depth(c, cam, d_tmp);
+    if (!rc) rc = launch_mesh_scene_depth(c, cam, d_tmp);
     hipError_t e = hipSuccess;
     if (!rc) e = hipMemcpyAsync(out, d_tmp, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     hipError_t e2 = hipStreamSynchronize(c->stream);

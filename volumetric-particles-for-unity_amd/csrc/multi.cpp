@@ -879,7 +879,7 @@ int multi_raymarch(vp_ctx* P, const vp_camera* cam, const vp_raymarch_params* rp
         k.ev_valid[1] = true;
         // (2) the slab's partial images
         float* keep = c->d_scene_depth;
-        if (!rp->scene_depth && c->n_occluders == 0) c->d_scene_depth = nullptr;
+        if (!rp->scene_depth && !has_occluders(c)) c->d_scene_depth = nullptr;
         RmHandoff ho{};
         ho.t_in = n_in ? k.d_tmaps : nullptr; ho.n_in = n_in; ho.plane = M->npix;
         ho.t_out0 = k.d_tout[0]; ho.t_out1 = k.d_tout[1]; ho.zsamples = (M->want_profile && !c->no_zprofile) ? c->d_zsamples : nullptr;   // the profile costs ~3 %: only when a re-cut was asked for
@@ -961,6 +961,19 @@ int multi_set_occluders(vp_ctx* P, const vp_occluder* boxes, int32_t n)
 {
     vp_multi* M = P->multi;
     return run_all(M, [&](Kid& k) -> int { const int rw = kid_wait(M, k, "vp_set_occluders (previous frame's exchanges)"); return rw ? rw : vp_set_occluders2(k.c, boxes, n); }, false);
+}
+
+// mesh occluders: every slab context holds the same shapes and instances and renders the same full maps
+int multi_set_occluder_meshes(vp_ctx* P, const vp_mesh* meshes, int32_t n)
+{
+    vp_multi* M = P->multi;
+    return run_all(M, [&](Kid& k) -> int { const int rw = kid_wait(M, k, "vp_set_occluder_meshes (previous frame's exchanges)"); return rw ? rw : vp_set_occluder_meshes(k.c, meshes, n); }, false);
+}
+
+int multi_set_occluder_instances(vp_ctx* P, const vp_mesh_instance* inst, int32_t n)
+{
+    vp_multi* M = P->multi;
+    return run_all(M, [&](Kid& k) -> int { const int rw = kid_wait(M, k, "vp_set_occluder_instances (previous frame's exchanges)"); return rw ? rw : vp_set_occluder_instances(k.c, inst, n); }, false);
 }
 
 vp_ctx* multi_owner_of_slice(vp_ctx* P, int zz)

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <vector>
 
 #include "../../include/vpfx.h"
 
@@ -17,6 +18,15 @@
 #define VPFX_CFG_NO_GREY_BRICKS 1
 // Test hook of the chained fill's watchdog: with the ENVIRONMENT variable VPFX_TEST_CHAIN_TIMEOUT=1 set when vp_create runs, the units await
 // tags nobody writes and give up after a few polls (error path).  Not reachable through the ABI structs.
+
+// mesh occluders (occluder_mesh.hip)
+struct MeshShape { int64_t first_vertex, n_vertices, first_triangle, n_triangles; };
+struct MeshInstDev {
+    float m[12];                  // object_to_world rows 0..2 (r*4 + c)
+    int32_t first_triangle, n_triangles;   // into d_mesh_idx
+    int32_t mirrored, pad;        // det(M3x3) < 0: b and c are swapped so that Cross(b - a, c - a) points outward
+};
+struct MeshTri { float4 p0, p1, p2; };   // world a.xyz b.x | b.yz c.xy | c.z, tile box (x0 | y0 << 16, x1 | y1 << 16), pad
 
 // ---------------------------------------------------------------------------------------------------
 // Kernel-constant PODs (passed by value as kernel arguments -> SGPRs / kernarg segment)
@@ -188,6 +198,19 @@ struct vp_ctx {
     unsigned occl_gen = 1, frame_gen = 1;                      // bumped by vp_set_occluders2 / vp_set_frame
     unsigned eye_depth_gen = 0; vp_camera eye_depth_cam{};
     unsigned light_depth_gen = 0, light_depth_frame = 0; float light_depth_planes[3] = {0.f, 0.f, 0.f};
+    // mesh occluders (occluder_mesh.hip): the shape list (all shapes' vertices / indices concatenated, indices rebased to the concatenation),
+    // the placed instances as the device reads them, and the per-view scratch both maps share (one stream: they never overlap)
+    float* d_mesh_pos = nullptr;                  // [total vertices][3]
+    int32_t* d_mesh_idx = nullptr;                // [total triangles][3]
+    std::vector<MeshShape> mesh_shapes;           // host copy of each shape's ranges
+    MeshInstDev* d_mesh_inst = nullptr;           // [n_mesh_inst] non-degenerate instances
+    uint32_t* d_mesh_inst_first = nullptr;        // [n_mesh_inst + 1] first instanced-triangle id of each instance (exclusive scan)
+    int n_mesh_inst = 0, n_mesh_inst_placed = 0;  // device instances (degenerate ones dropped) / instances the caller placed
+    uint32_t n_mesh_tris = 0;                     // instanced triangles of the device instances
+    MeshTri* d_mesh_rec = nullptr; size_t mesh_rec_cap = 0;            // [n_mesh_tris] per-view set-up records
+    uint32_t* d_mesh_tile_count = nullptr; unsigned long long* d_mesh_tile_start = nullptr; size_t mesh_tiles_cap = 0;  // [tiles (+1)]
+    uint32_t* d_mesh_list = nullptr; size_t mesh_list_cap = 0;         // per-tile triangle lists (CSR)
+    unsigned long long* h_mesh_total = nullptr;                         // pinned: the list length read back before the scatter
 
     // raymarch
     float4* d_mvtrans = nullptr;  // [brick_cap] per-brick translation column of _CameraToMetavoxel
@@ -306,3 +329,10 @@ int  vp_read_last_image(vp_ctx* c, const void* d_img, float* h_out);
 // occluders.hip
 int  launch_light_depth(vp_ctx* c, float nearz, float farz, float cam_dist, float* d_out);
 int  launch_scene_depth(vp_ctx* c, const vp_camera* cam, float* d_out);
+// occluder_mesh.hip: min() the placed mesh instances into a map launch_light_depth / launch_scene_depth wrote (no-op without instances)
+int  launch_mesh_light_depth(vp_ctx* c, float nearz, float farz, float cam_dist, float* d_out);
+int  launch_mesh_scene_depth(vp_ctx* c, const vp_camera* cam, float* d_out);
+void mesh_free_all(vp_ctx* c);
+inline bool has_occluders(const vp_ctx* c) { return c->n_occluders > 0 || c->n_mesh_inst_placed > 0; }
+int  multi_set_occluder_meshes(vp_ctx* c, const vp_mesh* meshes, int32_t n);
+int  multi_set_occluder_instances(vp_ctx* c, const vp_mesh_instance* inst, int32_t n);

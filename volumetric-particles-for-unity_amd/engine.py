@@ -245,6 +245,24 @@ class Engine:
     def set_occluders2(self, solids):
         self._ck(self.L.vp_set_occluders2(self.h, abi.as_occluders(solids) if len(solids) else None, len(solids)), "vp_set_occluders2")
 
+    def set_occluder_meshes(self, meshes):
+        """Occluder shapes: a list of (positions [V, 3] float, triangles [T, 3] int) in object space (Unity winding).  Replaces the list and
+        removes the placed instances (vp_set_occluder_meshes)."""
+        keep = []                                                      # the arrays stay alive for the call
+        arr = (abi.vp_mesh * max(1, len(meshes)))()
+        for i, (pos, tri) in enumerate(meshes):
+            p = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+            t = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+            keep += [p, t]
+            arr[i] = abi.vp_mesh(p.ctypes.data if p.size else None, t.ctypes.data if t.size else None, p.shape[0], t.shape[0])
+        self._ck(self.L.vp_set_occluder_meshes(self.h, arr if len(meshes) else None, len(meshes)), "vp_set_occluder_meshes")
+        del keep
+
+    def set_occluder_instances(self, instances):
+        """Placed shapes: a list of abi.vp_mesh_instance (scene.make_instance) -- vp_set_occluder_instances."""
+        arr = (abi.vp_mesh_instance * len(instances))(*instances) if len(instances) else None
+        self._ck(self.L.vp_set_occluder_instances(self.h, arr, len(instances)), "vp_set_occluder_instances")
+
     def render_light_depth(self, near=0.3, far=1000.0, cam_distance=200.0):
         out = np.empty((self.N[1] * self.nv, self.N[0] * self.nv), dtype=np.float32)
         self._ck(self.L.vp_render_light_depth(self.h, C.c_float(near), C.c_float(far), C.c_float(cam_distance), _vp(out)), "vp_render_light_depth")

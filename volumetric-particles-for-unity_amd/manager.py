@@ -62,6 +62,7 @@ class MetavoxelManager:
         self.lightDepthMap = None                                               # optional: the C# shim's OccluderSource.UnityDepthTextures
         self.sceneDepth = None                                                  # optional:   "
         self._occluders, self._occluders_dirty = [], False                      # the C# shim's OccluderSource.SceneMeshes
+        self._meshes, self._mesh_instances, self._meshes_dirty = None, [], False   # ... and .AllSceneMeshes (triangle meshes)
         self._engine = None
         self._frame_dirty = True
         self._cubemap_dirty = True
@@ -141,6 +142,11 @@ class MetavoxelManager:
         if self._occluders_dirty:
             self._engine.set_occluders2(self._occluders)
             self._occluders_dirty = False
+        if self._meshes_dirty:                                                  # the C# shim's OccluderSource.AllSceneMeshes: shapes when they changed,
+            if self._meshes is not None:                                        # instances whenever something moved
+                self._engine.set_occluder_meshes(self._meshes)
+            self._engine.set_occluder_instances(self._mesh_instances)
+            self._meshes, self._meshes_dirty = None, False
 
     # ---- the hot path ------------------------------------------------------------------------------------
     def UpdateMetavoxelPositions(self):
@@ -280,6 +286,13 @@ class MetavoxelManager:
         depth are then rendered on the GPU (what lightCamera.RenderWithShader and the main camera's depth buffer provide in the reference,
         VPR.cs:184,204).  Sent by the next SyncOccluders (= the next OnPostRender)."""
         self._occluders, self._occluders_dirty = list(solids), True
+
+    def SetOccluderMeshes(self, meshes, instances):
+        """Opaque scene geometry as triangle meshes: `meshes` = list of (positions [V, 3], triangles [T, 3]) in object space, or None to keep the
+        shapes already sent; `instances` = list of abi.vp_mesh_instance (scene.make_instance) placing them.  Combined with the solids by a per-pixel
+        minimum in both depth inputs (VPR.cs:184, 204).  Sent by the next SyncOccluders."""
+        self._meshes = None if meshes is None else list(meshes)
+        self._mesh_instances, self._meshes_dirty = list(instances), True
 
     def SetDisplacementTexture(self, cubemap):
         self.displacementCubemap = cubemap

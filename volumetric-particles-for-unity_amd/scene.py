@@ -362,3 +362,131 @@ def make_demo_scene(width=1024, height=768, warm_seconds=6.0, seed=7):
         unity_primitive(abi.VP_OCC_CYLINDER, (1.45, -1.05, 9.11), parent_position=par),                                                 # Cylinder 3
     ]
     return sc, em, boxes
+
+
+# ---- triangle-mesh occluders (ABI 6, additive: vp_set_occluder_meshes / vp_set_occluder_instances) ----------------------------------------
+# Unity winding: Cross(b - a, c - a) points out of the front face.  Every builder checks that its normals point outward.
+
+def _assert_outward(pos, tri, inner):
+    """inner(centroids) -> a point inside the solid near each triangle; the outward normal must point away from it."""
+    a, b, c = pos[tri[:, 0]], pos[tri[:, 1]], pos[tri[:, 2]]
+    n = np.cross(b - a, c - a)
+    cen = (a + b + c) / 3.0
+    assert np.all(np.einsum("ij,ij->i", n, cen - inner(cen)) > 0.0), "mesh normals must point outward"
+
+
+def unity_cube_mesh():
+    """Unity's Cube (mesh 10202): [-0.5, 0.5]^3, 24 vertices (4 per face), 12 triangles.  Returns (positions [24, 3] f32, triangles [12, 3] i32)."""
+    pos, tri = [], []
+    for axis in range(3):
+        for sgn in (-1.0, 1.0):
+            u, v = (axis + 1) % 3, (axis + 2) % 3
+            base = len(pos)
+            for du, dv in ((-0.5, -0.5), (0.5, -0.5), (0.5, 0.5), (-0.5, 0.5)):
+                p = [0.0, 0.0, 0.0]
+                p[axis], p[u], p[v] = 0.5 * sgn, du, dv
+                pos.append(p)
+            q = [base, base + 1, base + 2, base + 3]
+            # Cross(e_u, e_v) = +e_axis: keep the order on the + face, reverse it on the - face
+            tri += [[q[0], q[1], q[2]], [q[0], q[2], q[3]]] if sgn > 0 else [[q[0], q[2], q[1]], [q[0], q[3], q[2]]]
+    pos, tri = np.asarray(pos, np.float32), np.asarray(tri, np.int32)
+    _assert_outward(pos.astype(np.float64), tri, lambda c: np.zeros_like(c))
+    return pos, tri
+
+
+def prism_mesh(n=20, radius=0.5, half_height=1.0):
+    """An n-sided capped prism about the local y axis (Unity's Cylinder, mesh 10206: n = 20, radius 0.5, height 2)."""
+    ang = 2.0 * np.pi * np.arange(n) / n
+    ring = np.stack([radius * np.cos(ang), np.zeros(n), radius * np.sin(ang)], 1)
+    pos = np.concatenate([ring + [0, -half_height, 0], ring + [0, half_height, 0], [[0, -half_height, 0], [0, half_height, 0]]])
+    bc, tc = 2 * n, 2 * n + 1
+    tri = []
+    for i in range(n):
+        j = (i + 1) % n
+        tri += [[i, n + i, j], [j, n + i, n + j]]            # side (outward: Cross((0,2h,0), ring_j - ring_i) points out)
+        tri += [[bc, i, j], [tc, n + j, n + i]]              # caps
+    pos, tri = np.asarray(pos, np.float32), np.asarray(tri, np.int32)
+    _assert_outward(pos.astype(np.float64), tri, lambda c: np.zeros_like(c))
+    return pos, tri
+
+
+def icosphere_mesh(subdivisions=2, radius=0.5):
+    """Icosahedron subdivided `subdivisions` times, vertices on the sphere of `radius` (20 * 4^s triangles)."""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t],
+         [t, 0, -1], [t, 0, 1], [-t, 0, -1], [-t, 0, 1]]
+    f = [[0, 11, 5], [0, 5, 1], [0, 1, 7], [0, 7, 10], [0, 10, 11], [1, 5, 9], [5, 11, 4], [11, 10, 2], [10, 7, 6], [7, 1, 8],
+         [3, 9, 4], [3, 4, 2], [3, 2, 6], [3, 6, 8], [3, 8, 9], [4, 9, 5], [2, 4, 11], [6, 2, 10], [8, 6, 7], [9, 8, 1]]
+    verts = [np.asarray(p, np.float64) / np.linalg.norm(p) for p in v]
+    for _ in range(subdivisions):
+        mid, nf = {}, []
+
+        def m(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                p = verts[a] + verts[b]
+                verts.append(p / np.linalg.norm(p))
+                mid[key] = len(verts) - 1
+            return mid[key]
+        for a, b, c in f:
+            ab, bc, ca = m(a, b), m(b, c), m(c, a)
+            nf += [[a, ab, ca], [b, bc, ab], [c, ca, bc], [ab, bc, ca]]
+        f = nf
+    pos, tri = (np.asarray(verts) * radius).astype(np.float32), np.asarray(f, np.int32)
+    _assert_outward(pos.astype(np.float64), tri, lambda c: np.zeros_like(c))
+    return pos, tri
+
+
+def torus_mesh(major=0.5, minor=0.2, n_major=24, n_minor=12):
+    """A torus about the local y axis (non-convex)."""
+    u = 2.0 * np.pi * np.arange(n_major) / n_major
+    w = 2.0 * np.pi * np.arange(n_minor) / n_minor
+    U, Wv = np.meshgrid(u, w, indexing="ij")
+    r = major + minor * np.cos(Wv)
+    pos = np.stack([r * np.cos(U), minor * np.sin(Wv), r * np.sin(U)], -1).reshape(-1, 3)
+    tri = []
+    for i in range(n_major):
+        for j in range(n_minor):
+            a, b = i * n_minor + j, ((i + 1) % n_major) * n_minor + j
+            c, d = ((i + 1) % n_major) * n_minor + (j + 1) % n_minor, i * n_minor + (j + 1) % n_minor
+            tri += [[a, d, b], [b, d, c]]
+    pos, tri = pos.astype(np.float32), np.asarray(tri, np.int32)
+
+    def core(c):                                             # nearest point of the core circle
+        rr = np.hypot(c[:, 0], c[:, 2])
+        return np.stack([c[:, 0] / rr * major, np.zeros(len(c)), c[:, 2] / rr * major], 1)
+    _assert_outward(pos.astype(np.float64), tri, core)
+    return pos, tri
+
+
+def grid_mesh(nx, nz, size_x=1.0, size_z=1.0):
+    """A flat rectangle in the local y = 0 plane, facing +y, split into nx x nz quads (Unity's Plane is 10 x 10 quads of 10 units)."""
+    xs, zs = np.linspace(-0.5 * size_x, 0.5 * size_x, nx + 1), np.linspace(-0.5 * size_z, 0.5 * size_z, nz + 1)
+    X, Z = np.meshgrid(xs, zs, indexing="ij")
+    pos = np.stack([X, np.zeros_like(X), Z], -1).reshape(-1, 3).astype(np.float32)
+    tri = []
+    for i in range(nx):
+        for j in range(nz):
+            a, b, c, d = i * (nz + 1) + j, (i + 1) * (nz + 1) + j, (i + 1) * (nz + 1) + j + 1, i * (nz + 1) + j + 1
+            tri += [[a, d, c], [a, c, b]]                    # Cross((0,0,dz), (dx,0,dz)) = +y
+    tri = np.asarray(tri, np.int32)
+    _assert_outward(pos.astype(np.float64), tri, lambda c: c - [0.0, 1.0, 0.0])
+    return pos, tri
+
+
+def make_instance(mesh_index, object_to_world) -> abi.vp_mesh_instance:
+    """A placed occluder shape: object_to_world = 4 x 4 affine matrix (row-major numpy, as written on paper), sent column-major."""
+    inst = abi.vp_mesh_instance()
+    m = np.asarray(object_to_world, dtype=np.float64).reshape(4, 4)
+    for i, x in enumerate(m.T.reshape(16)):
+        inst.object_to_world[i] = float(x)
+    inst.mesh = int(mesh_index)
+    return inst
+
+
+def box_instance_matrix(box) -> np.ndarray:
+    """The object_to_world that places unity_cube_mesh() exactly on an occluder box (vp_obb / vp_occluder of type VP_OCC_BOX): the box is
+    {p : |axes (p - center)|_k <= half_extent_k}, so the inverse of `axes` (= its transpose when the rows are orthonormal) maps the cube onto it.
+    (trs with a per-axis scale: rot3 * scale multiplies column k by scale[k].)"""
+    axes = np.asarray(list(box.axes), dtype=np.float64).reshape(3, 3)          # rows = the box's unit axes
+    return trs(list(box.center), np.linalg.inv(axes), [2.0 * h for h in box.half_extent])
