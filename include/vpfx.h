@@ -40,7 +40,9 @@ extern "C" {
                                 6: same struct layouts; new: vp_occluder / vp_set_occluders2 (cylinder and ellipsoid occluders beside boxes).
                                    Stricter since 5: vp_emitter_config.reserved[] must be 0 and .lifetime finite, <= 1e5 s (VP_ERR_BAD_ARG otherwise)
                                 6 (additive): mesh occluders -- vp_mesh / vp_mesh_instance, vp_set_occluder_meshes / vp_set_occluder_instances; no
-                                   existing layout or entry point changed: a host detects the feature by the presence of the symbols */
+                                   existing layout or entry point changed: a host detects the feature by the presence of the symbols
+                                6 (additive): particles that stay on the GPU -- vp_upload_particles_device, vp_device_emitter_*,
+                                   vp_upload_particles_from_emitter, vp_emitter_schedule; detected by the presence of the symbols as well */
 
 typedef enum vp_status {
     VP_OK = 0,
@@ -562,6 +564,41 @@ int  vp_emitter_count(const vp_emitter* em);
 /* Write the live particles (oldest first) as records of `layout` (each zeroed, then position, size, rotation -- degrees or radians as the
  * layout says --, lifetime, startLifetime): the array vp_bin / vp_upload_particles take.  Returns the records written (<= capacity). */
 int  vp_emitter_write_particles(const vp_emitter* em, void* particles_out, int32_t capacity, const vp_particle_layout* layout);
+
+/* ABI 6 (additive): particles that never leave the GPU.
+ * vp_upload_particles_device is vp_upload_particles for records that already live in memory of the context's device (hipMalloc, or managed
+ * memory accessible there): same validation, same state, the same extract; the records are copied device to device on the context's stream
+ * and there is NO host wait -- the caller keeps the buffer unchanged until the work queued so far has finished (vp_sync, or an event of its
+ * own).  The pointer is checked before anything is queued: unregistered or pinned host memory, memory of another device, records that run
+ * past the end of the allocation and NULL with count > 0 are VP_ERR_BAD_ARG.  A fan-out context returns VP_ERR_UNSUPPORTED.  A refused
+ * call leaves the previously uploaded particles in effect. */
+int  vp_upload_particles_device(vp_ctx* ctx, const void* d_particles, int32_t count, const vp_particle_layout* layout,
+                                const float psys_local_to_world[16]);
+/* The particle source above, simulated in device memory: the same vp_emitter_config (and its validation), the same PCG32 stream, the same
+ * arithmetic and the same prewarm switch as vp_emitter_*.  For one config and one sequence of dt both emitters agree bit for bit on the live
+ * count after every step, the order, lifetime, rotation, size and startLifetime; positions pass through the device's sqrt / sin / cos
+ * instead of the host's and agree to a few ulp of the cloud's extent.  The emitter belongs to ONE single-device context (a fan-out context:
+ * VP_ERR_UNSUPPORTED); its kernels are queued on the context's current stream and no call but the parity probe waits for them.  The host
+ * follows the live range of birth indices itself (vp_emitter_schedule), so a step reads nothing back.  vp_destroy(ctx) frees the device arrays
+ * of the context's emitters and orphans them: every call then returns VP_ERR_STATE, and vp_device_emitter_destroy frees the host part.
+ * Thread safety is the context's. */
+typedef struct vp_device_emitter vp_device_emitter;
+int  vp_device_emitter_create(vp_ctx* ctx, const vp_emitter_config* cfg, vp_device_emitter** out);   /* reserved[0] = 1: prewarms on the device */
+void vp_device_emitter_destroy(vp_device_emitter* em);
+/* Advance by dt seconds (move / age / retire, then emit): queues kernels, never waits.  Returns the live count (>= 0) or a negative
+ * vp_status; a negative or non-finite dt is VP_ERR_BAD_ARG and changes nothing. */
+int  vp_device_emitter_step(vp_device_emitter* em, float dt);
+int  vp_device_emitter_count(const vp_device_emitter* em);
+/* Parity probe: the live particles (oldest first) as records of `layout`, as vp_emitter_write_particles writes them.  Waits for the stream. */
+int  vp_device_emitter_read_particles(vp_device_emitter* em, void* particles_out, int32_t capacity, const vp_particle_layout* layout);
+/* vp_upload_particles with the emitter's live particles (oldest first = particle index) as the source: packed on the device straight into
+ * the context's record buffer, then the usual extract.  No host wait; vp_bin_resident, vp_fill and vp_raymarch* follow as usual.  An
+ * emitter of another context is VP_ERR_BAD_ARG. */
+int  vp_upload_particles_from_emitter(vp_ctx* ctx, vp_device_emitter* em, const float psys_local_to_world[16]);
+/* Host only, needs no device (like vp_plan_slabs): the live range [first_out[i], next_out[i]) of birth indices after step i of the dt
+ * sequence -- all particles share one lifetime, so they die oldest first and the live set is always such a range.  With reserved[0] = 1 the
+ * prewarm steps run first.  This is the bookkeeping both vp_device_emitter_step and (implicitly) vp_emitter_step follow. */
+int  vp_emitter_schedule(const vp_emitter_config* cfg, const float* dts, int32_t n_steps, int64_t* first_out, int64_t* next_out);
 
 /* ---- parity probes / stats ------------------------------------------------------------------ */
 int  vp_get_mv_positions(vp_ctx* ctx, float* pos_out /* [Nz][Ny][Nx][3] */);

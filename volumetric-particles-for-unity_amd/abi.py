@@ -248,6 +248,8 @@ EXPORTED_SYMBOLS = [
     "vp_get_multi_info", "vp_rebalance", "vp_rccl_unique_id", "vp_plan_slabs", "vp_blend_plan", "vp_exchange_plan",
     "vp_unity_render_event_func", "vp_unity_set_frame_desc", "vp_unity_register_output", "vp_unity_register_output_fd", "vp_unity_last_status", "vp_unity_clear_slot",
     "vp_emitter_default_config", "vp_emitter_create", "vp_emitter_destroy", "vp_emitter_step", "vp_emitter_count", "vp_emitter_write_particles",
+    "vp_upload_particles_device", "vp_device_emitter_create", "vp_device_emitter_destroy", "vp_device_emitter_step", "vp_device_emitter_count",
+    "vp_device_emitter_read_particles", "vp_upload_particles_from_emitter", "vp_emitter_schedule",
 ]
 class vp_xop(C.Structure):
     """One operation of the image exchange's message schedule (vp_exchange_plan)."""

@@ -360,6 +360,7 @@ void vp_destroy_single(vp_ctx* c)
                    c->d_lightmap, c->d_cubequads, c->d_depthmap, c->d_occluders, c->d_mvtrans, c->d_brick_hit, c->d_rank, c->d_tile_order, c->d_tile_curve, c->d_image, c->d_scene_depth, c->d_samples, c->d_zsamples, c->d_cellinfo, c->d_occmask};
     for (void* p : dev) if (p) (void)hipFree(p);
     mesh_free_all(c);
+    device_emitters_orphan_all(c);
     if (c->h_chain_err) (void)hipHostFree(c->h_chain_err);
     if (c->h_meta_host) (void)hipHostFree(c->h_meta_host);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
@@ -439,7 +440,14 @@ VP_EXPORT int vp_upload_particles(vp_ctx* c, const void* particles, int32_t coun
 
 int api_upload_particles(vp_ctx* c, const void* particles, int32_t count, const vp_particle_layout* lay, const float* psys_local_to_world, bool sync)
 {
-    if ((!particles && count > 0) || count < 0 || !lay || !psys_local_to_world)
+    UploadSource src;
+    src.host = particles;
+    return api_upload_particles_from(c, src, count, lay, psys_local_to_world, sync);
+}
+
+int api_upload_particles_from(vp_ctx* c, const UploadSource& src, int32_t count, const vp_particle_layout* lay, const float* psys_local_to_world, bool sync)
+{
+    if ((!src.host && !src.device && !src.produce && count > 0) || count < 0 || !lay || !psys_local_to_world)
         return vp_fail(c, VP_ERR_BAD_ARG, "vp_upload_particles: null/negative argument");
     const int32_t offs[5] = {lay->off_position + 8, lay->off_size, lay->off_rotation, lay->off_lifetime, lay->off_start_lifetime};
     if (lay->stride < 4) return vp_fail(c, VP_ERR_BAD_ARG, "vp_upload_particles: stride %d", lay->stride);
@@ -467,7 +475,9 @@ int api_upload_particles(vp_ctx* c, const void* particles, int32_t count, const 
     c->lay = *lay;
     hl_build_psys(c, psys_local_to_world);
     if (count > 0) {
-        VP_HIP(hipMemcpyAsync(c->d_raw, particles, bytes, hipMemcpyHostToDevice, c->stream));
+        if (src.produce) { rc = src.produce(c, src.user); if (rc) return rc; }
+        else if (src.device) VP_HIP(hipMemcpyAsync(c->d_raw, src.device, bytes, hipMemcpyDeviceToDevice, c->stream));
+        else VP_HIP(hipMemcpyAsync(c->d_raw, src.host, bytes, hipMemcpyHostToDevice, c->stream));
         rc = launch_extract(c); if (rc) return rc;
         if (sync) { int rcs = stream_sync(c); if (rcs) return rcs; }     // caller's array is not retained past return (the fan-out syncs all devices itself)
     }

@@ -212,6 +212,9 @@ struct vp_ctx {
     uint32_t* d_mesh_list = nullptr; size_t mesh_list_cap = 0;         // per-tile triangle lists (CSR)
     unsigned long long* h_mesh_total = nullptr;                         // pinned: the list length read back before the scatter
 
+    // device particle sources created on this context (emitter_device.hip): vp_destroy frees their device arrays and orphans them
+    std::vector<vp_device_emitter*> emitters;
+
     // raymarch
     float4* d_mvtrans = nullptr;  // [brick_cap] per-brick translation column of _CameraToMetavoxel
     size_t mvtrans_cap = 0;
@@ -305,6 +308,18 @@ int  vp_create_single(const vp_config* cfg, vp_ctx** out);
 void vp_destroy_single(vp_ctx* c);
 int  api_stream_sync(vp_ctx* c);
 int  api_upload_particles(vp_ctx* c, const void* particles, int32_t count, const vp_particle_layout* lay, const float* psys_l2w, bool sync);
+// Where the records of an upload come from -- exactly one of: host memory (copied; `sync` waits for the copy), memory of the context's device
+// (copied on the stream, never waited for), or a producer that writes `count` records of `lay` into c->d_raw itself on the stream (the
+// device emitter's pack kernel).  Validation, capacity growth, the extract and the state flags are one code path for all three.
+struct UploadSource {
+    const void* host = nullptr;
+    const void* device = nullptr;
+    int (*produce)(vp_ctx* c, void* user) = nullptr;
+    void* user = nullptr;
+};
+int  api_upload_particles_from(vp_ctx* c, const UploadSource& src, int32_t count, const vp_particle_layout* lay, const float* psys_l2w, bool sync);
+// emitter_device.hip
+void device_emitters_orphan_all(vp_ctx* c);            // vp_destroy: free the device arrays of the context's emitters and detach them
 int  api_stage_fill_inputs(vp_ctx* c, const vp_fill_params* p);
 int  api_ensure_bricks(vp_ctx* c, bool need_scratch);
 int  api_stage_raymarch(vp_ctx* c, const vp_camera* cam, const vp_raymarch_params* rp, RmConsts* k);

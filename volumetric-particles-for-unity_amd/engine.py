@@ -60,6 +60,15 @@ def lib():
         L.vp_emitter_default_config.restype = None
         L.vp_emitter_count.argtypes = [C.c_void_p]
         L.vp_emitter_step.argtypes = [C.c_void_p, C.c_float]
+        L.vp_upload_particles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.vp_device_emitter_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_device_emitter_destroy.restype = None
+        L.vp_device_emitter_destroy.argtypes = [C.c_void_p]
+        L.vp_device_emitter_step.argtypes = [C.c_void_p, C.c_float]
+        L.vp_device_emitter_count.argtypes = [C.c_void_p]
+        L.vp_device_emitter_read_particles.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.vp_upload_particles_from_emitter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_emitter_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -134,6 +143,18 @@ class Engine:
         p = np.ascontiguousarray(particles)
         m = np.ascontiguousarray(psys_local_to_world, dtype=np.float32)
         self._ck(self.L.vp_upload_particles(self.h, _vp(p), C.c_int32(len(p)), C.byref(layout), _vp(m)), "vp_upload_particles")
+
+    def upload_particles_device(self, d_particles: int, count: int, layout, psys_local_to_world):
+        """vp_upload_particles_device: `count` records of `layout` at the device address `d_particles` (memory of this context's device, e.g. a
+        torch tensor's data_ptr()).  Queued on the context's stream and not waited for: keep the buffer unchanged until sync()."""
+        m = np.ascontiguousarray(psys_local_to_world, dtype=np.float32)
+        self._ck(self.L.vp_upload_particles_device(self.h, C.c_void_p(d_particles), C.c_int32(count), C.byref(layout), _vp(m)),
+                 "vp_upload_particles_device")
+
+    def upload_particles_from_emitter(self, em, psys_local_to_world):
+        """vp_upload_particles_from_emitter: the live particles of a scene.DeviceEmitter of this engine, oldest first; no host round trip."""
+        m = np.ascontiguousarray(psys_local_to_world, dtype=np.float32)
+        self._ck(self.L.vp_upload_particles_from_emitter(self.h, em.h, _vp(m)), "vp_upload_particles_from_emitter")
 
     def bin_resident(self):
         self._ck(self.L.vp_bin_resident(self.h), "vp_bin_resident")

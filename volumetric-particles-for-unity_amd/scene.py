@@ -325,6 +325,63 @@ class DemoEmitter:
             pass
 
 
+class DeviceEmitter:
+    """The same particle source simulated in device memory (`vp_device_emitter_*`, csrc/emitter_device.hip): it belongs to one single-GPU
+    `engine.Engine`, `step` queues kernels on the engine's stream and `Engine.upload_particles_from_emitter` bins its particles without a
+    host round trip.  `particles()` is the parity probe (waits, copies to the host).  Close it before, or after, the engine -- after the
+    engine is closed every call but `close` fails with VP_ERR_STATE."""
+
+    def __init__(self, engine, seed=7, **overrides):
+        self.L = engine.L
+        cfg = abi.vp_emitter_config()
+        self.L.vp_emitter_default_config(C.byref(cfg))
+        cfg.seed = seed
+        for k, v in overrides.items():
+            if k == "prewarm":
+                cfg.reserved[0] = 1 if v else 0
+                continue
+            assert hasattr(cfg, k), k
+            setattr(cfg, k, v)
+        self.cfg = cfg
+        self.h = C.c_void_p()
+        rc = self.L.vp_device_emitter_create(engine.h, C.byref(cfg), C.byref(self.h))
+        if rc:
+            raise ValueError(f"vp_device_emitter_create -> {abi.STATUS_NAMES.get(rc, rc)}")
+        self.layout = particle_layout(False)
+
+    def step(self, dt):
+        n = self.L.vp_device_emitter_step(self.h, C.c_float(dt))
+        if n < 0:
+            raise ValueError(f"vp_device_emitter_step -> {abi.STATUS_NAMES.get(n, n)}")
+        return n
+
+    def count(self):
+        n = self.L.vp_device_emitter_count(self.h)
+        if n < 0:
+            raise ValueError(f"vp_device_emitter_count -> {abi.STATUS_NAMES.get(n, n)}")
+        return n
+
+    def particles(self, layout=None):
+        lay = self.layout if layout is None else layout
+        n = self.count()
+        p = np.zeros(n, dtype=PARTICLE_DTYPE)
+        got = self.L.vp_device_emitter_read_particles(self.h, p.ctypes.data_as(C.c_void_p), n, C.byref(lay))
+        if got != n:
+            raise ValueError(f"vp_device_emitter_read_particles -> {abi.STATUS_NAMES.get(got, got)} (expected {n})")
+        return p
+
+    def close(self):
+        if self.h:
+            self.L.vp_device_emitter_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def make_demo_scene(width=1024, height=768, warm_seconds=6.0, seed=7):
     """The reference's scene: 10^3 metavoxels x 32^3 voxels of size 3 (scene:9013-9016), main camera at (-10,0,-20) looking
     +z with fov 60, directional light quaternion (0.1856,0,0,0.9826), grid centre at world (0,-5,0), particle system at world
