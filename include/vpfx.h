@@ -42,7 +42,9 @@ extern "C" {
                                 6 (additive): mesh occluders -- vp_mesh / vp_mesh_instance, vp_set_occluder_meshes / vp_set_occluder_instances; no
                                    existing layout or entry point changed: a host detects the feature by the presence of the symbols
                                 6 (additive): particles that stay on the GPU -- vp_upload_particles_device, vp_device_emitter_*,
-                                   vp_upload_particles_from_emitter, vp_emitter_schedule; detected by the presence of the symbols as well */
+                                   vp_upload_particles_from_emitter, vp_emitter_schedule; detected by the presence of the symbols as well
+                                6 (additive): where the resident particles are and what the bin kept of them -- vp_particle_bounds,
+                                   vp_particle_coverage, vp_fit_grid (host only); detected by the presence of the symbols as well */
 
 typedef enum vp_status {
     VP_OK = 0,
@@ -599,6 +601,72 @@ int  vp_upload_particles_from_emitter(vp_ctx* ctx, vp_device_emitter* em, const 
  * sequence -- all particles share one lifetime, so they die oldest first and the live set is always such a range.  With reserved[0] = 1 the
  * prewarm steps run first.  This is the bookkeeping both vp_device_emitter_step and (implicitly) vp_emitter_step follow. */
 int  vp_emitter_schedule(const vp_emitter_config* cfg, const float* dts, int32_t n_steps, int64_t* first_out, int64_t* next_out);
+
+/* ABI 6 (additive): where the resident particles are, and what the bin kept of them.
+ * With device-resident particles the host never sees a position, yet vp_set_frame needs a grid_center and a cloud that drifts out of the
+ * grid drops out of the bins silently.  Three calls close that gap without reading the particles back:
+ *
+ * vp_particle_bounds -- one reduction over the particles of the last upload (any source): boxes of the centres and of the spheres
+ *   (centre -/+ |size| / 2 on every axis) in a caller-chosen RIGID frame, the largest radius, and how many particles entered.
+ *   world_to_frame is column-major like every matrix of the ABI: Camera.worldToCameraMatrix gives the reference's AABBForParticles
+ *   (Assets/Main Scene/AABBForParticles.cs:26-62), the light's worldToLocal gives the box a grid must hold, NULL = world space.
+ *   Arithmetic (f32, no FMA): with M(r,c) = m[c*4 + r] and (x, y, z, size) the world position and size the upload extracted,
+ *   f_r = ((M(r,0) x + M(r,1) y) + M(r,2) z) + M(r,3), h = |size| * 0.5, sphere box = f_r - h / f_r + h.  Minimum and maximum are exact
+ *   and order-free: the result is defined to the bit (up to the sign of a zero).  A particle is skipped exactly when the bin skips it
+ *   (x, y, z or size not finite); counted + skipped = the uploaded count.  counted = 0: every min is +INFINITY, every max -INFINITY,
+ *   max_radius 0.  VP_ERR_BAD_ARG: null out, a non-finite entry, a last row other than 0 0 0 1, or rows of the 3x3 part that miss
+ *   orthonormality by more than 1e-3 in any dot product (a sphere's extent along a frame axis is its radius only in a rigid frame).
+ *   VP_ERR_STATE before an upload; an upload of 0 particles is valid.  Fan-out context: VP_ERR_UNSUPPORTED.  Costs one wait on the
+ *   context's stream.  A refused call changes nothing.
+ *
+ * vp_particle_coverage -- which particles the last vp_bin* put into at least one metavoxel list of the owned slab.  Counted from the lists
+ *   the bin built (no acceptance test is repeated, so it cannot disagree with the bin): covered + uncovered + skipped = particles,
+ *   pairs = vp_stats.pairs.  uncovered > 0 with a grid that contains the cloud is reference behaviour (integer N/2 origin against float
+ *   binning, VPR.cs:388 / 422-438: with an even metavoxel count a particle smaller than half a metavoxel is looked up in one candidate cell
+ *   only).  mv_per_particle_out: optional host array [particles], the number of lists each particle is in.  VP_ERR_STATE before vp_bin*;
+ *   fan-out context: VP_ERR_UNSUPPORTED.  One wait on the stream.
+ *
+ * vp_fit_grid -- host only, needs no device (like vp_plan_slabs): the grid_center at which num_mv metavoxels of mv_scale hold the
+ *   light-space box [ls_min, ls_max] (sphere_min / sphere_max of a vp_particle_bounds taken in the light's worldToLocal frame).
+ *   Metavoxel xx is centred at lsO + (xx - N/2) s with INTEGER N/2 (UpdateMetavoxelPositions, VPR.cs:370-394): the grid spans
+ *   lsO + [-(N/2) - 0.5, N - N/2 - 0.5] s, half a metavoxel below lsO when N is even.  Per axis: c = (lo + hi) / 2 + (N even ? s / 2 : 0);
+ *   snap > 0: c = rint(c / snap) * snap (snapped in light space -- pass the voxel size s / (nv - 2b) and the voxel lattice does not swim
+ *   when a moving cloud is refitted); box_min = c - (N/2 + 0.5) s, box_max = box_min + N s; fits / clipped are evaluated after snapping;
+ *   min_mv_scale = max over the axes of (hi - lo + snap) / N; grid_center = light_to_world * ls_center.  Computed in double.
+ *   VP_ERR_BAD_ARG: null pointer, light_to_world not rigid (the rule above), lo > hi or non-finite bounds, num_mv < 1, mv_scale not
+ *   finite or <= 0, snap negative or not finite.
+ *
+ * The two result records are plain struct tags (no typedef): their names are the functions'. */
+struct vp_particle_bounds {
+    float   center_min[3], center_max[3];  /* box of the particle centres, in the frame              */
+    float   sphere_min[3], sphere_max[3];  /* box of the spheres: centre -/+ |size| / 2 on every axis */
+    float   max_radius;                    /* largest |size| / 2                                      */
+    int32_t counted;                       /* finite particles that entered the boxes                 */
+    int32_t skipped;                       /* non-finite position or size: the rule vp_bin skips by   */
+    int32_t reserved;                      /* 0                                                       */
+};                                         /* 64 bytes */
+int  vp_particle_bounds(vp_ctx* ctx, const float world_to_frame[16], struct vp_particle_bounds* out);
+struct vp_particle_coverage {
+    int32_t particles;            /* uploaded                                                        */
+    int32_t covered;              /* in the list of >= 1 metavoxel of the owned slab                 */
+    int32_t uncovered;            /* finite, in none                                                 */
+    int32_t skipped;              /* non-finite                                                      */
+    int64_t pairs;                /* sum of the per-particle counts = vp_stats.pairs                 */
+    int32_t max_mv_per_particle;
+    int32_t reserved;
+};                                /* 32 bytes */
+int  vp_particle_coverage(vp_ctx* ctx, struct vp_particle_coverage* out, int32_t* mv_per_particle_out);
+typedef struct vp_grid_fit {
+    float   grid_center[3];       /* world space: hand to vp_set_frame                                        */
+    float   ls_center[3];         /* the same point in the light's local space                                */
+    float   box_min[3], box_max[3]; /* light space: what the metavoxels of that grid span                    */
+    float   min_mv_scale;         /* smallest mv_scale at which num_mv metavoxels hold the input box          */
+    int32_t fits;                 /* 1: input box inside [box_min, box_max] on every axis                     */
+    int32_t clipped;              /* bit k: low side of axis k sticks out; bit 3 + k: high side               */
+    int32_t reserved;
+} vp_grid_fit;                    /* 64 bytes */
+int  vp_fit_grid(const float light_to_world[16], const float ls_min[3], const float ls_max[3], const int32_t num_mv[3],
+                 float mv_scale, float snap, vp_grid_fit* out);
 
 /* ---- parity probes / stats ------------------------------------------------------------------ */
 int  vp_get_mv_positions(vp_ctx* ctx, float* pos_out /* [Nz][Ny][Nx][3] */);

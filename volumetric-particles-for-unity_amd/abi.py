@@ -202,6 +202,24 @@ class vp_emitter_config(C.Structure):
                 ("reserved", C.c_int32 * 6)]
 
 
+class vp_particle_bounds(C.Structure):
+    """ABI 6 (additive): boxes of the resident particles' centres and spheres in a rigid frame (vp_particle_bounds); 64 bytes."""
+    _fields_ = [("center_min", C.c_float * 3), ("center_max", C.c_float * 3), ("sphere_min", C.c_float * 3), ("sphere_max", C.c_float * 3),
+                ("max_radius", C.c_float), ("counted", C.c_int32), ("skipped", C.c_int32), ("reserved", C.c_int32)]
+
+
+class vp_particle_coverage(C.Structure):
+    """ABI 6 (additive): which particles the last bin put into at least one metavoxel list (vp_particle_coverage); 32 bytes."""
+    _fields_ = [("particles", C.c_int32), ("covered", C.c_int32), ("uncovered", C.c_int32), ("skipped", C.c_int32), ("pairs", C.c_int64),
+                ("max_mv_per_particle", C.c_int32), ("reserved", C.c_int32)]
+
+
+class vp_grid_fit(C.Structure):
+    """ABI 6 (additive): the grid centre at which num_mv metavoxels hold a light-space box (vp_fit_grid, host only); 64 bytes."""
+    _fields_ = [("grid_center", C.c_float * 3), ("ls_center", C.c_float * 3), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3),
+                ("min_mv_scale", C.c_float), ("fits", C.c_int32), ("clipped", C.c_int32), ("reserved", C.c_int32)]
+
+
 class vp_stats(C.Structure):
     _fields_ = [
         ("particles", C.c_int64),
@@ -250,6 +268,7 @@ EXPORTED_SYMBOLS = [
     "vp_emitter_default_config", "vp_emitter_create", "vp_emitter_destroy", "vp_emitter_step", "vp_emitter_count", "vp_emitter_write_particles",
     "vp_upload_particles_device", "vp_device_emitter_create", "vp_device_emitter_destroy", "vp_device_emitter_step", "vp_device_emitter_count",
     "vp_device_emitter_read_particles", "vp_upload_particles_from_emitter", "vp_emitter_schedule",
+    "vp_particle_bounds", "vp_particle_coverage", "vp_fit_grid",
 ]
 class vp_xop(C.Structure):
     """One operation of the image exchange's message schedule (vp_exchange_plan)."""

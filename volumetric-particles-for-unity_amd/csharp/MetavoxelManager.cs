@@ -27,6 +27,27 @@ using UnityEngine;
 
 namespace MetavoxelEngine
 {
+    // ABI 6 (additive): result records of the particle queries.  vp_particle_bounds is the name of the record AND of the function in the
+    // header, so the two records the class imports a function for live here, outside the class that declares the imports.
+    [StructLayout(LayoutKind.Sequential)]
+    struct vp_particle_bounds              // boxes of the resident particles in a rigid frame (64 bytes)
+    {
+        [MarshalAs(UnmanagedType.ByValArray, SizeConst = 3)] public float[] center_min;
+        [MarshalAs(UnmanagedType.ByValArray, SizeConst = 3)] public float[] center_max;
+        [MarshalAs(UnmanagedType.ByValArray, SizeConst = 3)] public float[] sphere_min;
+        [MarshalAs(UnmanagedType.ByValArray, SizeConst = 3)] public float[] sphere_max;
+        public float max_radius; public int counted, skipped, reserved;
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    struct vp_grid_fit                     // the grid centre that holds a light-space box (64 bytes)
+    {
+        [MarshalAs(UnmanagedType.ByValArray, SizeConst = 3)] public float[] grid_center;
+        [MarshalAs(UnmanagedType.ByValArray, SizeConst = 3)] public float[] ls_center;
+        [MarshalAs(UnmanagedType.ByValArray, SizeConst = 3)] public float[] box_min;
+        [MarshalAs(UnmanagedType.ByValArray, SizeConst = 3)] public float[] box_max;
+        public float min_mv_scale; public int fits, clipped, reserved;
+    }
+
     [RequireComponent(typeof(Camera))]
     public class MetavoxelManager : MonoBehaviour
     {
@@ -174,6 +195,8 @@ namespace MetavoxelEngine
         [DllImport(LIB)] static extern int vp_unity_last_status(int slot, out ulong eventsRun);
         [DllImport(LIB)] static extern int vp_unity_clear_slot(int slot);
         [DllImport(LIB)] static extern int vp_unity_register_output_fd(int slot, IntPtr ctx, int fd, ulong bytes, ulong offset);   // texture interop: the exported render-texture memory
+        [DllImport(LIB)] static extern int vp_particle_bounds(IntPtr ctx, float[] worldToFrame, out vp_particle_bounds bounds);   // null frame = world space
+        [DllImport(LIB)] static extern int vp_fit_grid(float[] lightToWorld, float[] lsMin, float[] lsMax, int[] numMv, float mvScale, float snap, out vp_grid_fit fit);
 
         IntPtr ctx = IntPtr.Zero;
         ParticleSystem.Particle[] parts;
@@ -502,6 +525,32 @@ namespace MetavoxelEngine
         {
             Vector3 g = wsGridCenter;
             Check(vp_set_frame(ctx, ToArray(dirLight.transform.localToWorldMatrix), new float[] { g.x, g.y, g.z }), "vp_set_frame");
+        }
+
+        // ---- where the particles are (never called from OnPreRender / OnPostRender: the host decides when to refit) ----
+        // Moves gridCenter to where the particles uploaded last are: their sphere box in the light's space -> vp_fit_grid -> the GameObject the
+        // frame reads.  snap < 0: one voxel (the voxel lattice does not swim when a moving cloud is refitted); 0: no snap.  Returns false when a
+        // call failed or the cloud is larger than the grid.
+        public bool FitGridToParticles(float snap)
+        {
+            if (snap < 0f) snap = mvScale.x / (numVoxelsInMetavoxel - 2 * numBorderVoxels);
+            vp_particle_bounds b; vp_grid_fit fit;
+            if (!Check(vp_particle_bounds(ctx, ToArray(dirLight.transform.worldToLocalMatrix), out b), "vp_particle_bounds") || b.counted == 0) return false;
+            int[] n = new int[] { numMetavoxelsX, numMetavoxelsY, numMetavoxelsZ };
+            if (!Check(vp_fit_grid(ToArray(dirLight.transform.localToWorldMatrix), b.sphere_min, b.sphere_max, n, mvScale.x, snap, out fit), "vp_fit_grid")) return false;
+            gridCenter.transform.position = new Vector3(fit.grid_center[0], fit.grid_center[1], fit.grid_center[2]);   // picked up by the next frame (VPR.cs:189)
+            return fit.fits != 0;
+        }
+
+        // The reference's AABBForParticles.FindAABB (AABBForParticles.cs:26-62) over the particles uploaded last: the spheres' box in the main
+        // camera's space.  Camera space looks down -z: `max` takes the smallest z, `min` the largest (:43-55), as the reference does.
+        public Bounds ParticleAABB()
+        {
+            vp_particle_bounds b;
+            if (!Check(vp_particle_bounds(ctx, ToArray(Camera.main.worldToCameraMatrix), out b), "vp_particle_bounds") || b.counted == 0) return new Bounds();
+            Vector3 max = new Vector3(b.sphere_max[0], b.sphere_max[1], b.sphere_min[2]);
+            Vector3 min = new Vector3(b.sphere_min[0], b.sphere_min[1], b.sphere_max[2]);
+            return new Bounds((max + min) / 2.0f, max - min);
         }
 
         void BinParticlesToMetavoxels()                                    // VPR.cs:397-457

@@ -361,6 +361,7 @@ void vp_destroy_single(vp_ctx* c)
     for (void* p : dev) if (p) (void)hipFree(p);
     mesh_free_all(c);
     device_emitters_orphan_all(c);
+    particle_queries_free(c);
     if (c->h_chain_err) (void)hipHostFree(c->h_chain_err);
     if (c->h_meta_host) (void)hipHostFree(c->h_meta_host);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
@@ -1187,5 +1188,22 @@ VP_EXPORT int vp_blend_plan(int32_t world, const int32_t* cuts, int32_t z_bounda
     for (int r = 0; r < world; ++r)
         if (cuts[r] >= cuts[r + 1]) return vp_fail(nullptr, VP_ERR_BAD_ARG, "vp_blend_plan: slab %d is empty", r);
     *n_plan = hl_blend_plan(world, cuts, z_boundary, chain_out, plan_rank, plan_which, plan_kind, straddler);
+    return VP_OK;
+}
+
+VP_EXPORT int vp_fit_grid(const float light_to_world[16], const float ls_min[3], const float ls_max[3], const int32_t num_mv[3], float mv_scale,
+                          float snap, vp_grid_fit* out)
+{
+    if (!light_to_world || !ls_min || !ls_max || !num_mv || !out) return vp_fail(nullptr, VP_ERR_BAD_ARG, "vp_fit_grid: null argument");
+    if (!hl_is_rigid(light_to_world))
+        return vp_fail(nullptr, VP_ERR_BAD_ARG, "vp_fit_grid: light_to_world is not a finite rigid transform (rows orthonormal within 1e-3, last row 0 0 0 1)");
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(ls_min[k]) || !std::isfinite(ls_max[k]) || ls_min[k] > ls_max[k])
+            return vp_fail(nullptr, VP_ERR_BAD_ARG, "vp_fit_grid: axis %d of the box is [%g, %g]", k, (double)ls_min[k], (double)ls_max[k]);
+        if (num_mv[k] < 1) return vp_fail(nullptr, VP_ERR_BAD_ARG, "vp_fit_grid: num_mv[%d] = %d", k, num_mv[k]);
+    }
+    if (!std::isfinite(mv_scale) || !(mv_scale > 0.f)) return vp_fail(nullptr, VP_ERR_BAD_ARG, "vp_fit_grid: mv_scale %g", (double)mv_scale);
+    if (!std::isfinite(snap) || snap < 0.f) return vp_fail(nullptr, VP_ERR_BAD_ARG, "vp_fit_grid: snap %g", (double)snap);
+    hl_fit_grid(light_to_world, ls_min, ls_max, num_mv, mv_scale, snap, out);
     return VP_OK;
 }

@@ -428,3 +428,42 @@ int hl_exchange_plan(int world, int rank, int strad, int all_gather, int phase, 
     return n;
 }
 
+// ---- particle queries (include/vpfx.h "where the resident particles are") ---------------------------------------------------------------
+// The frames vp_particle_bounds and vp_fit_grid accept: a sphere's extent along a frame axis is its radius only when the frame is rigid.
+bool hl_is_rigid(const float m[16])
+{
+    for (int i = 0; i < 16; ++i) if (!std::isfinite(m[i])) return false;
+    if (cm(m, 3, 0) != 0.f || cm(m, 3, 1) != 0.f || cm(m, 3, 2) != 0.f || cm(m, 3, 3) != 1.f) return false;
+    for (int i = 0; i < 3; ++i)
+        for (int j = i; j < 3; ++j) {
+            double d = 0.0;
+            for (int k = 0; k < 3; ++k) d += (double)cm(m, i, k) * (double)cm(m, j, k);
+            if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-3)) return false;
+        }
+    return true;
+}
+
+// UpdateMetavoxelPositions centres metavoxel xx at lsO + (xx - N/2) s with INTEGER N/2 (VPR.cs:370-394, hl_build_grid above): the grid spans
+// lsO + [-(N/2) - 0.5, N - N/2 - 0.5] s -- half a metavoxel below lsO when N is even.  In double; the outputs are rounded once.
+void hl_fit_grid(const float l2w[16], const float lo[3], const float hi[3], const int32_t num_mv[3], float mv_scale, float snap, vp_grid_fit* out)
+{
+    const double s = (double)mv_scale, q = (double)snap;
+    double c[3], need = 0.0;
+    vp_grid_fit f{};
+    for (int k = 0; k < 3; ++k) {
+        const double l = (double)lo[k], h = (double)hi[k];
+        const int n = num_mv[k];
+        c[k] = (l + h) / 2.0 + (n % 2 == 0 ? s / 2.0 : 0.0);
+        if (q > 0.0) c[k] = std::rint(c[k] / q) * q;
+        const double bmin = c[k] - ((double)(n / 2) + 0.5) * s, bmax = bmin + (double)n * s;
+        if (l < bmin) f.clipped |= 1 << k;
+        if (h > bmax) f.clipped |= 1 << (3 + k);
+        need = std::max(need, (h - l + q) / (double)n);
+        f.ls_center[k] = (float)c[k]; f.box_min[k] = (float)bmin; f.box_max[k] = (float)bmax;
+    }
+    for (int r = 0; r < 3; ++r)
+        f.grid_center[r] = (float)((((double)cm(l2w, r, 0) * c[0] + (double)cm(l2w, r, 1) * c[1]) + (double)cm(l2w, r, 2) * c[2]) + (double)cm(l2w, r, 3));
+    f.min_mv_scale = (float)need;
+    f.fits = f.clipped == 0 ? 1 : 0;
+    *out = f;
+}

@@ -215,6 +215,12 @@ struct vp_ctx {
     // device particle sources created on this context (emitter_device.hip): vp_destroy frees their device arrays and orphans them
     std::vector<vp_device_emitter*> emitters;
 
+    // particle queries (particle_bounds.hip): allocated by the first query, never touched by the frame path
+    uint32_t* d_query = nullptr;  // [QUERY_WORDS] result words the query kernels reduce into
+    uint32_t* h_query = nullptr;  // the same words in pinned host memory (copied on the stream, read after the wait)
+    int* d_cover = nullptr;       // [cover_cap] metavoxel lists each particle is in (vp_particle_coverage)
+    size_t cover_cap = 0;
+
     // raymarch
     float4* d_mvtrans = nullptr;  // [brick_cap] per-brick translation column of _CameraToMetavoxel
     size_t mvtrans_cap = 0;
@@ -278,6 +284,10 @@ int    hl_blend_plan(int world, const int* cuts, int zb, int* chain, int* plan_r
 int    hl_exchange_plan(int world, int rank, int strad, int all_gather, int phase, vp_xop* ops, int cap);     // message schedule of the image exchange (vp_exchange_plan)
 void   hl_chain_groups(int world, int rm_groups, int* group_of_pos /* [world]: group of chain position p */);
 void   hl_build_rm_consts(const vp_ctx* c, const vp_camera* cam, const vp_raymarch_params* rp, RmConsts* k);
+// a column-major 4x4 that is finite, affine (last row 0 0 0 1) and whose 3x3 rows are orthonormal within 1e-3 in every dot product
+bool   hl_is_rigid(const float m[16]);
+// the grid centre at which num_mv metavoxels of mv_scale hold a light-space box (vp_fit_grid; arguments already validated)
+void   hl_fit_grid(const float l2w[16], const float lo[3], const float hi[3], const int32_t num_mv[3], float mv_scale, float snap, vp_grid_fit* out);
 
 // bin.hip
 int  launch_extract(vp_ctx* c);
@@ -320,6 +330,8 @@ struct UploadSource {
 int  api_upload_particles_from(vp_ctx* c, const UploadSource& src, int32_t count, const vp_particle_layout* lay, const float* psys_l2w, bool sync);
 // emitter_device.hip
 void device_emitters_orphan_all(vp_ctx* c);            // vp_destroy: free the device arrays of the context's emitters and detach them
+// particle_bounds.hip
+void particle_queries_free(vp_ctx* c);                 // vp_destroy: the scratch of vp_particle_bounds / vp_particle_coverage
 int  api_stage_fill_inputs(vp_ctx* c, const vp_fill_params* p);
 int  api_ensure_bricks(vp_ctx* c, bool need_scratch);
 int  api_stage_raymarch(vp_ctx* c, const vp_camera* cam, const vp_raymarch_params* rp, RmConsts* k);

@@ -69,6 +69,9 @@ def lib():
         L.vp_device_emitter_read_particles.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.vp_upload_particles_from_emitter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.vp_emitter_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.vp_particle_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_particle_coverage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_fit_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         _lib = L
     return _lib
 
@@ -169,6 +172,35 @@ class Engine:
         n = C.c_int32(0)
         self._ck(self.L.vp_read_binlist(self.h, int(xx), int(yy), int(zz), _vp(ids), cap, C.byref(n)), "vp_read_binlist")
         return ids[: n.value].copy()
+
+    # -- where the resident particles are (no read-back of the particles) --------------------------------
+    def particle_bounds(self, world_to_frame=None):
+        """vp_particle_bounds: boxes of the uploaded particles' centres and spheres in the rigid frame `world_to_frame` (column-major 16
+        floats; None = world space), the largest radius and the counted / skipped particles.  One wait on the stream."""
+        m = None if world_to_frame is None else np.ascontiguousarray(world_to_frame, dtype=np.float32)
+        b = abi.vp_particle_bounds()
+        self._ck(self.L.vp_particle_bounds(self.h, None if m is None else _vp(m), C.byref(b)), "vp_particle_bounds")
+        return _as_dict(b)
+
+    def particle_coverage(self, per_particle=False):
+        """vp_particle_coverage: how many particles the last bin put into at least one metavoxel list of the owned slab (counted from the
+        lists themselves).  per_particle=True adds "mv_per_particle": int32 [particles], the number of lists each particle is in."""
+        cov = abi.vp_particle_coverage()
+        per = np.zeros(int(self.stats()["particles"]), dtype=np.int32) if per_particle else None
+        self._ck(self.L.vp_particle_coverage(self.h, C.byref(cov), None if per is None or per.size == 0 else _vp(per)), "vp_particle_coverage")
+        out = _as_dict(cov)
+        if per_particle:
+            out["mv_per_particle"] = per
+        return out
+
+    def fit_grid_to_particles(self, light_to_world, snap=0.0):
+        """The grid centre that holds the resident particles: their sphere box in the light's local space (particle_bounds in the inverse of
+        the rigid `light_to_world`) through fit_grid with this engine's metavoxel counts and scale.  Returns the fit (see fit_grid); hand
+        its "grid_center" to set_frame."""
+        bounds = self.particle_bounds(rigid_inverse(light_to_world))
+        if bounds["counted"] == 0:
+            raise ValueError("fit_grid_to_particles: no finite particle is resident")
+        return fit_grid(light_to_world, bounds["sphere_min"], bounds["sphere_max"], self.N, self.cfg.mv_scale, snap)
 
     # -- fill ----------------------------------------------------------------------------------------
     def fill(self, params):
@@ -384,6 +416,41 @@ def exchange_plan(world: int, rank: int, straddler, all_gather: bool, phase: int
     if rc:
         raise VpfxError("vp_exchange_plan", rc, lib().vp_last_error(None).decode())
     return [ops[i] for i in range(n.value)]
+
+
+def fit_grid(light_to_world, ls_min, ls_max, num_mv, mv_scale, snap=0.0):
+    """vp_fit_grid (host only; no GPU needed): the grid centre at which `num_mv` metavoxels of `mv_scale` hold the light-space box
+    [ls_min, ls_max], snapped to multiples of `snap` in light space when snap > 0.  Returns a dict of the vp_grid_fit fields."""
+    l = np.ascontiguousarray(light_to_world, dtype=np.float32)
+    lo, hi = np.ascontiguousarray(ls_min, dtype=np.float32), np.ascontiguousarray(ls_max, dtype=np.float32)
+    n = np.ascontiguousarray(num_mv, dtype=np.int32)
+    if l.size != 16 or lo.size != 3 or hi.size != 3 or n.size != 3:
+        raise ValueError("fit_grid: light_to_world[16], ls_min[3], ls_max[3], num_mv[3] expected")
+    fit = abi.vp_grid_fit()
+    rc = lib().vp_fit_grid(_vp(l), _vp(lo), _vp(hi), _vp(n), C.c_float(mv_scale), C.c_float(snap), C.byref(fit))
+    if rc:
+        raise VpfxError("vp_fit_grid", rc, lib().vp_last_error(None).decode())
+    return _as_dict(fit)
+
+
+def rigid_inverse(m16) -> np.ndarray:
+    """worldToLocal of a rigid column-major transform, in float32 with the operations of the library's own light inverse (rows = the
+    transposed rotation, translation = -((r.x t.x + r.y t.y) + r.z t.z)): a point transformed by it lands where the binning puts it."""
+    m = np.ascontiguousarray(m16, dtype=np.float32).reshape(4, 4).T          # (row, col)
+    inv = np.zeros((4, 4), dtype=np.float32)
+    inv[:3, :3] = m[:3, :3].T
+    t = m[:3, 3]
+    for k in range(3):
+        r = inv[k, :3]
+        inv[k, 3] = -((r[0] * t[0] + r[1] * t[1]) + r[2] * t[2])
+    inv[3, 3] = 1.0
+    return np.ascontiguousarray(inv.T.reshape(16))
+
+
+def _as_dict(st):
+    """A result struct as a dict: scalars as Python numbers, float[3] members as float32 arrays; `reserved` left out."""
+    return {k: (np.array(getattr(st, k), dtype=np.float32) if isinstance(getattr(st, k), C.Array) else getattr(st, k))
+            for k, _ in st._fields_ if k != "reserved"}
 
 
 def _copy_cfg(cfg):

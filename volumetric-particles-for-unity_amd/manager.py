@@ -281,6 +281,30 @@ class MetavoxelManager:
         self.wsGridCenter = np.ascontiguousarray(pos, dtype=np.float32)
         self._frame_dirty = True                                                # gridCenter moved: VPR.cs:189
 
+    # ---- where the particles are (never called from OnPreRender / OnPostRender: a host decides when to refit) ----
+    def FitGridToParticles(self, snap=None):
+        """Move the grid centre to where the particles uploaded last are: their sphere box in light space (vp_particle_bounds) -> vp_fit_grid
+        -> SetGridCenter.  `snap` = lattice the centre is snapped to in light space (default: one voxel, mvScale / (nv - 2 border), so the
+        voxels do not swim when a moving cloud is refitted; 0 = no snap).  Returns the fit; fit["fits"] == 0 means the cloud is larger than
+        the grid (fit["min_mv_scale"] would hold it)."""
+        if snap is None:
+            snap = self.mvScale / float(self.numVoxelsInMetavoxel - 2 * self.numBorderVoxels)
+        fit = self._engine.fit_grid_to_particles(self.lightToWorld, snap)
+        self.SetGridCenter(fit["grid_center"])
+        return fit
+
+    def ParticleAABB(self, camera):
+        """The reference's AABBForParticles.FindAABB (AABBForParticles.cs:26-62) over the particles uploaded last: the box of the spheres in
+        the main camera's space as Unity's Bounds (centre, size).  Camera space looks down -z, so the reference's `max` takes the SMALLEST z
+        and `min` the largest (:43-55) and size.z comes out negative, as in the reference.  Without a finite particle: zeros (:32)."""
+        b = self._engine.particle_bounds([camera.world_to_camera[i] for i in range(16)])
+        if b["counted"] == 0:
+            return np.zeros(3, dtype=np.float32), np.zeros(3, dtype=np.float32)
+        lo, hi = b["sphere_min"], b["sphere_max"]
+        mx = np.array([hi[0], hi[1], lo[2]], dtype=np.float32)
+        mn = np.array([lo[0], lo[1], hi[2]], dtype=np.float32)
+        return (mx + mn) / np.float32(2.0), mx - mn                            # new Bounds((max + min) / 2.0f, max - min)   :60
+
     def SetOccluders(self, solids):
         """Opaque scene geometry as solids (abi.vp_obb boxes / abi.vp_occluder boxes, cylinders, ellipsoids): the light depth map and the eye
         depth are then rendered on the GPU (what lightCamera.RenderWithShader and the main camera's depth buffer provide in the reference,
