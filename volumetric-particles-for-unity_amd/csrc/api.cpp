@@ -281,6 +281,7 @@ int vp_create_single(const vp_config* cfg, vp_ctx** out)
     // test hooks are honoured only by contexts that opt in through vp_config (VP_MULTI_TEST_HOOKS): a stray environment variable never
     // changes what a production context does
     if (cfg->multi_flags & VP_MULTI_TEST_HOOKS) { const char* hook = getenv("VPFX_TEST_CHAIN_TIMEOUT"); c->test_chain_timeout = hook && hook[0] == '1'; }
+    { const char* sw = getenv("VPFX_RM_NO_SPACE_SKIP"); c->rm_space_skip = !sw ? 0 : sw[0] == '1' ? -1 : sw[0] == '0' ? 1 : 0; }   // -1 never, 1 always, 0 default rule
 #if VPFX_AB    // measurement switches of A/B builds (make EXTRA=-DVPFX_AB=1); the shipped library never reads them
     { const char* sw = getenv("VPFX_NO_ZPROFILE"); c->no_zprofile = sw && sw[0] == '1'; }
     { const char* sw = getenv("VPFX_RM_FLAT"); c->rm_flat = sw && sw[0] == '1'; }
@@ -357,7 +358,7 @@ void vp_destroy_single(vp_ctx* c)
     if (c->stream) (void)hipStreamSynchronize(c->stream); else (void)hipDeviceSynchronize();
     void* dev[] = {c->d_mvPos, c->d_raw, c->d_ws, c->d_rec, c->d_count, c->d_offsets, c->d_cursor, c->d_brick_index,
                    c->d_occ_list, c->d_ids_tmp, c->d_ids, c->d_onecol, c->d_work_counter, c->d_ord, c->d_colcount, c->d_chain, c->d_cube_u8, c->d_meta, c->d_scan_totals, c->d_bricks, c->d_dens_ao,
-                   c->d_lightmap, c->d_cubequads, c->d_depthmap, c->d_occluders, c->d_mvtrans, c->d_brick_hit, c->d_rank, c->d_tile_order, c->d_tile_curve, c->d_image, c->d_scene_depth, c->d_samples, c->d_zsamples, c->d_cellinfo, c->d_occmask};
+                   c->d_lightmap, c->d_cubequads, c->d_depthmap, c->d_occluders, c->d_mvtrans, c->d_brick_hit, c->d_rank, c->d_tile_order, c->d_tile_curve, c->d_image, c->d_scene_depth, c->d_samples, c->d_zsamples, c->d_cellinfo, c->d_occmask, c->d_slab_rect};
     for (void* p : dev) if (p) (void)hipFree(p);
     mesh_free_all(c);
     device_emitters_orphan_all(c);

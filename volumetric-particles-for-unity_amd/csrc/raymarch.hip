@@ -102,6 +102,34 @@ __device__ __forceinline__ void column_rank(const RmConsts& k, const float* __re
     if (chunk == 0 && i < nxy) rank_out[i] = partial[threadIdx.x];
 }
 
+// The rectangle of slab zz's occupied cells for k_raymarch's empty-slab skipping: out[zz] = x0 | x1 << 5 | y0 << 10 | y1 << 21 (Nx <= 32,
+// Ny <= 1024); a slab that is empty or not owned gets y0 = 2047.  One trailing workgroup of k_rm_prepare per slab; it reads brick_index only
+// (nothing this launch writes) and owns its word, so the table needs no clear in front.
+__device__ __forceinline__ void slab_rect(const RmConsts& k, const int* __restrict__ brick_index, uint32_t* __restrict__ out, const int zz)
+{
+    __shared__ int part[4][4];
+    const int nxy = k.Nx * k.Ny, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int x0 = 31, x1 = 0, y0 = 2047, y1 = 0;
+    if (zz >= k.z0 && zz < k.z1) {
+        const int* occ = brick_index + (size_t)zz * nxy;
+        for (int c = threadIdx.x; c < nxy; c += 256)
+            if (occ[c] >= 0) {
+                const int y = c / k.Nx, x = c - y * k.Nx;
+                x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
+            }
+    }
+    for (int o = 32; o; o >>= 1) {
+        x0 = min(x0, __shfl_xor(x0, o)); x1 = max(x1, __shfl_xor(x1, o));
+        y0 = min(y0, __shfl_xor(y0, o)); y1 = max(y1, __shfl_xor(y1, o));
+    }
+    if (lane == 0) { part[wave][0] = x0; part[wave][1] = x1; part[wave][2] = y0; part[wave][3] = y1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) { x0 = min(x0, part[w][0]); x1 = max(x1, part[w][1]); y0 = min(y0, part[w][2]); y1 = max(y1, part[w][3]); }
+        out[zz] = (uint32_t)x0 | (uint32_t)x1 << 5 | (uint32_t)y0 << 10 | (uint32_t)y1 << 21;
+    }
+}
+
 // Everything the march needs per frame in ONE launch over all N^3 cells (it was four memsets and a kernel over the occupied metavoxels):
 // the translation column of _CameraToMetavoxel = TRS(mvPos, lightRot, s).inverse * cameraToWorld of every occupied metavoxel (VPR.cs:774-778,
 // same operation order as the matrix product the reference does per draw) into mvtrans[slot] and into the cell's record, "empty" records for the other cells, the
@@ -109,8 +137,10 @@ __device__ __forceinline__ void column_rank(const RmConsts& k, const float* __re
 __global__ void __launch_bounds__(256)
 k_rm_prepare(RmConsts k, const int* __restrict__ brick_index, const float* __restrict__ mvPos, int n3, float4* __restrict__ mvtrans,
              float4* __restrict__ cellinfo /* nullable */, uint32_t* __restrict__ occmask /* nullable */, int* __restrict__ brick_hit,
-             unsigned long long* __restrict__ samples, int nprep, int sgx, float* __restrict__ cost_out, int ncost, int* __restrict__ rank_out)
+             unsigned long long* __restrict__ samples, int nprep, int sgx, float* __restrict__ cost_out, int ncost, int* __restrict__ rank_out,
+             int nrank, uint32_t* __restrict__ rect_out)
 {
+    if ((int)blockIdx.x >= nprep + ncost + nrank) { slab_rect(k, brick_index, rect_out, (int)blockIdx.x - nprep - ncost - nrank); return; }   // (launched when the march skips empty slabs)
     if ((int)blockIdx.x >= nprep + ncost) { column_rank(k, mvPos, rank_out, (int)blockIdx.x - nprep - ncost); return; }
     // workgroups past the cells' own: one super-tile's cost estimate each (tile_cost; it reads brick_index only -- nothing this launch writes).
     // One launch instead of two: a frame of the reference's scene is 0.24 ms and a launch is 4 us of it.
@@ -202,6 +232,13 @@ int launch_raymarch(vp_ctx* c, const RmConsts& k_in, float* d_over, float* d_und
 {
     RmConsts k = k_in;
     k.occ_lds = (VPFX_RM_OCC_LDS && VPFX_RM_CELLINFO && k.Nx <= 32 && k.Nz * k.Ny <= VPFX_RM_OCC_WORDS) ? 1 : 0;
+    // empty-slab skipping (bit 1): the kernels without flag paths, on grids whose rectangles fit k_raymarch's LDS table beside the bitmask
+    // -- and in launches that do not fit the GPU at once (rm_ordered's rule: more than two waves per SIMD).  A resident launch ends with its
+    // slowest wave whatever the others skip, and the rectangles' workgroups and the test per slab cost C1 (1 024 waves, 8 slabs) +0.8 % of its frame.
+    const long long waves = (long long)rm_num_super_tiles(k.W, k.H) * (4 << (VPFX_RM_LX + VPFX_RM_LY));
+    const bool skip = k.occ_lds && k.Nz <= VPFX_RM_SKIP_RECTS && !(k.flags & ~VP_RM_NO_EARLY_OUT) &&
+                      (c->rm_space_skip > 0 || (c->rm_space_skip == 0 && waves > (long long)c->num_cus * 8));
+    if (skip) k.occ_lds |= 2;
     const RmHandoff ho = (handoff && d_under) ? *handoff : RmHandoff{};          // slab (partial-image) kernels only
     const int early_out = (c->cfg.no_early_out == 1 || (k.flags & (VP_RM_NO_EARLY_OUT | VP_RM_SHOW_NUM_SAMPLES | VP_RM_SHOW_BLEND_FUNC | VP_RM_SHOW_DRAW_ORDER))) ? 0 : 1;
     k.flags &= ~VP_RM_NO_EARLY_OUT;                     // a launch switch, not a path of the FLAGS kernels
@@ -221,6 +258,7 @@ int launch_raymarch(vp_ctx* c, const RmConsts& k_in, float* d_over, float* d_und
 #if VPFX_RM_CELLINFO
     if (!c->d_cellinfo) VP_HIP(hipMalloc((void**)&c->d_cellinfo, c->n3 * sizeof(float4)));
     if (k.occ_lds && !c->d_occmask) VP_HIP(hipMalloc((void**)&c->d_occmask, VPFX_RM_OCC_WORDS * sizeof(uint32_t)));
+    if (skip && !c->d_slab_rect) VP_HIP(hipMalloc((void**)&c->d_slab_rect, VPFX_RM_SKIP_RECTS * sizeof(uint32_t)));
 #endif
     c->brick_hit_n = nocc;
     // one launch prepares the frame: translations, per-cell records, occupancy rows, cleared hit flags and sample counter, and -- its trailing
@@ -232,9 +270,9 @@ int launch_raymarch(vp_ctx* c, const RmConsts& k_in, float* d_over, float* d_und
         const bool ordered = rm_ordered(c, k);
         float* cost = reinterpret_cast<float*>(c->d_tile_order + rm_order_ints(nsuper));
         const int ncost = ordered ? nsuper : 0, nrank = (k.Nx * k.Ny + RM_RANK_COLS - 1) / RM_RANK_COLS;
-        hipLaunchKernelGGL(k_rm_prepare, dim3((unsigned)(nprep + ncost + nrank)), dim3(256), 0, c->stream, k, c->d_brick_index, c->d_mvPos,
+        hipLaunchKernelGGL(k_rm_prepare, dim3((unsigned)(nprep + ncost + nrank + (skip ? k.Nz : 0))), dim3(256), 0, c->stream, k, c->d_brick_index, c->d_mvPos,
                            (int)c->n3, c->d_mvtrans, c->d_cellinfo, k.occ_lds ? c->d_occmask : (uint32_t*)nullptr, c->d_brick_hit, c->d_samples,
-                           nprep, rm_super_tiles_x(k.W), cost, ncost, c->d_rank);
+                           nprep, rm_super_tiles_x(k.W), cost, ncost, c->d_rank, nrank, c->d_slab_rect);
     }
     if (nocc > 0) {
         if (k.flags & VP_RM_SHOW_DRAW_ORDER)

@@ -518,7 +518,8 @@ __global__ void __launch_bounds__(64, (PARTIAL && FLAGS) ? VPFX_RM_WAVES_PARTIAL
 k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restrict__ bricks, const float4* __restrict__ mvtrans,
            const int* __restrict__ rank, const float* __restrict__ scene_depth, float4* __restrict__ img_over, float4* __restrict__ img_under,
            unsigned long long* __restrict__ samples, int* __restrict__ brick_hit, const int* __restrict__ tile_order, int early_out,
-           RmHandoff ho, const float4* __restrict__ cellinfo, const uint32_t* __restrict__ occmask, int order_len)
+           RmHandoff ho, const float4* __restrict__ cellinfo, const uint32_t* __restrict__ occmask, int order_len,
+           const uint32_t* __restrict__ slab_rect)
 {
     const int lane = threadIdx.x;
     // XCD-aware tile order: workgroup b lands on XCD b % 8 (observed dispatch order; used for speed only), and each XCD
@@ -545,9 +546,17 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
     // load (31 % of the wave time sat in the walk, scripts/raymarch_phase_profile.py).  The grid's occupancy is one bit per cell: 4 KB at
     // 32^3, copied into LDS by the wave (one round trip for the whole copy), so that only occupied cells go to memory for their record.
     __shared__ uint32_t s_occ[VPFX_RM_OCC_WORDS];
+    // Empty-slab skipping (k.occ_lds & 2): the rectangle [x0, x1] x [y0, y1] of every slab's occupied cells (k_rm_prepare: slab_rect), here as
+    // the four thresholds the slab loop compares the ray's (x, y) range with: (x0 - 1, x1 + 2, y0 - 1, y1 + 2)
+    __shared__ float4 s_rect[VPFX_RM_SKIP_RECTS];
     if (!FLAGS && k.occ_lds) {
         const int nw = k.Nz * k.Ny;
         for (int i = lane; i < nw; i += 64) s_occ[i] = occmask[i];
+        if ((k.occ_lds & 2) && lane < k.Nz) {
+            const uint32_t r = slab_rect[lane];                 // x0 | x1 << 5 | y0 << 10 | y1 << 21; an empty slab has y0 = 2047: every ray misses it
+            s_rect[lane] = make_float4((float)((int)(r & 31u) - 1), (float)((int)((r >> 5) & 31u) + 2), (float)((int)((r >> 10) & 2047u) - 1),
+                                       (float)((int)(r >> 21) + 2));
+        }
         __syncthreads();
     }
 #endif
@@ -635,6 +644,19 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
             dst = F4{0.f, 0.f, 0.f, 0.f};
             storedA = true;
         }
+#if VPFX_RM_OCC_LDS
+        // Skip the slab when the ray cannot meet an occupied cell in it.  The walk below is monotone between the cells that hold the ray's
+        // positions at ta and at tb, and a tie at a cell corner moves it by at most one cell: no cell outside the box of those two cells,
+        // widened by ONE cell on every side, is ever offered.  If that box misses the rectangle of the slab's occupied cells the walk finds
+        // nothing, blends nothing and leaves dst, the sample count and `done` as they are -- so does the skip.  (Skip only: the walk of a slab
+        // that is not skipped starts where it always did; a walk relocated to the rectangle loses the occasional sample, see below.)
+        // floor(max) + 1 < x0  <=>  max < x0 - 1;  floor(min) - 1 > x1  <=>  min >= x1 + 2.
+        if (!FLAGS && (k.occ_lds & 2)) {
+            const float4 rc = s_rect[zz];
+            const float xa = fmaf(ta, R.dgx, R.ogx), xb = fmaf(tb, R.dgx, R.ogx), ya = fmaf(ta, R.dgy, R.ogy), yb = fmaf(tb, R.dgy, R.ogy);
+            if (fmaxf(xa, xb) < rc.x || fminf(xa, xb) >= rc.y || fmaxf(ya, yb) < rc.z || fminf(ya, yb) >= rc.w) continue;
+        }
+#endif
         F4 d = dst;
         const int* occ = brick_index + zz * nxy;
         int last = over ? 0x7fffffff : -1;
@@ -1192,7 +1214,7 @@ void launch_rm_variant(vp_ctx* c, const RmConsts& k, float* d_over, float* d_und
     const dim3 grid(((order_len + 7) / 8) * 8 * (4 << (VPFX_RM_LX + VPFX_RM_LY))), block(64);
     hipLaunchKernelGGL((k_raymarch<NV, PARTIAL, WRAP, FLAGS, GREY>), grid, block, 0, c->stream, k, c->d_brick_index, c->d_bricks, c->d_mvtrans,
                        c->d_rank, c->d_scene_depth, (float4*)d_over, (float4*)d_under, c->d_samples, c->d_brick_hit, order, early_out, ho,
-                       (const float4*)c->d_cellinfo, (const uint32_t*)c->d_occmask, order_len);
+                       (const float4*)c->d_cellinfo, (const uint32_t*)c->d_occmask, order_len, (const uint32_t*)c->d_slab_rect);
 }
 
 #if VPFX_AB

@@ -69,7 +69,7 @@ struct RmConsts {
     int W, H, Nx, Ny, Nz, nv, z0, z1;
     int zB, steps, soft, partial;
     int wave_lx;                  // log2 of the ray-march wave's pixel-block extent along the lane-fastest screen axis: 3 = 8 x 8, 4 = 16 x 4, 5 = 32 x 2 (k_raymarch)
-    int flags, num_covered, lane_transpose, occ_lds;  // (occ_lds: the grid's occupancy bitmask fits k_raymarch's LDS copy, launch_raymarch)  VP_RM_* bits of vp_raymarch_params.flags; _NumMetavoxelsCovered (VPR.cs:755); lanes run down screen columns
+    int flags, num_covered, lane_transpose, occ_lds;  // (occ_lds: bit 0 = the grid's occupancy bitmask fits k_raymarch's LDS copy, bit 1 = the slabs' rectangles are used too; launch_raymarch)  VP_RM_* bits of vp_raymarch_params.flags; _NumMetavoxelsCovered (VPR.cs:755); lanes run down screen columns
     float aspect, neg_inv_tan, zMin, s;
     float mvStep, inv_mvStep, nearc, farc;
     float c2m_lin[9];             // linear part of _CameraToMetavoxel (identical for every MV), rows     VPR.cs:778
@@ -82,6 +82,10 @@ struct RmConsts {
     float inv_soft;
     float alpha_cutoff;           // early-out once (1 - dst.a) <= cutoff in the UNDER phase (0 = exact only)
 };
+// Empty-slab skipping of k_raymarch (raymarch.hip: slab_rect): d_slab_rect holds one packed word per light-axis slab, the rectangle of its
+// occupied cells; a ray skips the slabs whose rectangle its (x, y) range in the slab, widened by one cell, misses.  RmConsts.occ_lds carries
+// the switch: bit 0 = the occupancy bitmask is in LDS, bit 1 = so are the rectangles.
+#define VPFX_RM_SKIP_RECTS 64     // slabs the LDS table of k_raymarch holds (taller grids keep the plain walk)
 
 // Cross-slab saturation hand-off of the ray-march (slab kernels only; raymarch.hip).  The reference's single render target sees every
 // metavoxel (VPR.cs:652-711), so one GPU stops a ray as soon as it is saturated; a slab on its own only knows its own metavoxels.
@@ -224,6 +228,9 @@ struct vp_ctx {
     // raymarch
     float4* d_mvtrans = nullptr;  // [brick_cap] per-brick translation column of _CameraToMetavoxel
     size_t mvtrans_cap = 0;
+    int rm_space_skip = 0;        // VPFX_RM_NO_SPACE_SKIP in the environment at vp_create (test switch: parity of the two paths, A/B timing): 1 = the ray-march walks
+                                  // every slab (-1 here), 0 = it skips empty slabs in every launch, also the small ones launch_raymarch leaves alone (1 here); unset = the default rule (0)
+    uint32_t* d_slab_rect = nullptr; // [VPFX_RM_SKIP_RECTS] per-slab rectangle of the occupied cells (k_rm_prepare -> k_raymarch's LDS)
     uint32_t* d_occmask = nullptr; // [Nz][Ny] one bit per cell (Nx <= 32): occupied metavoxels, copied into LDS by k_raymarch for the cell walk
     float4* d_cellinfo = nullptr; // [N^3] (translation, brick slot | -1) per cell: VPFX_RM_CELLINFO A/B variant of the cell walk
     int* d_rank = nullptr;        // [Ny*Nx] draw-order rank of the (yy, xx) columns for this frame's camera (VPR.cs:613-632), written by k_rm_prepare
