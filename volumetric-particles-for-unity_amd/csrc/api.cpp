@@ -282,6 +282,7 @@ int vp_create_single(const vp_config* cfg, vp_ctx** out)
     // changes what a production context does
     if (cfg->multi_flags & VP_MULTI_TEST_HOOKS) { const char* hook = getenv("VPFX_TEST_CHAIN_TIMEOUT"); c->test_chain_timeout = hook && hook[0] == '1'; }
     { const char* sw = getenv("VPFX_RM_NO_SPACE_SKIP"); c->rm_space_skip = !sw ? 0 : sw[0] == '1' ? -1 : sw[0] == '0' ? 1 : 0; }   // -1 never, 1 always, 0 default rule
+    { const char* sw = getenv("VPFX_RM_NO_BOX_CLIP"); c->rm_box_clip = !sw ? 0 : sw[0] == '1' ? -1 : sw[0] == '0' ? 1 : 0; }          // -1 never, 1 always, 0 default rule
 #if VPFX_AB    // measurement switches of A/B builds (make EXTRA=-DVPFX_AB=1); the shipped library never reads them
     { const char* sw = getenv("VPFX_NO_ZPROFILE"); c->no_zprofile = sw && sw[0] == '1'; }
     { const char* sw = getenv("VPFX_RM_FLAT"); c->rm_flat = sw && sw[0] == '1'; }
@@ -358,7 +359,7 @@ void vp_destroy_single(vp_ctx* c)
     if (c->stream) (void)hipStreamSynchronize(c->stream); else (void)hipDeviceSynchronize();
     void* dev[] = {c->d_mvPos, c->d_raw, c->d_ws, c->d_rec, c->d_count, c->d_offsets, c->d_cursor, c->d_brick_index,
                    c->d_occ_list, c->d_ids_tmp, c->d_ids, c->d_onecol, c->d_work_counter, c->d_ord, c->d_colcount, c->d_chain, c->d_cube_u8, c->d_meta, c->d_scan_totals, c->d_bricks, c->d_dens_ao,
-                   c->d_lightmap, c->d_cubequads, c->d_depthmap, c->d_occluders, c->d_mvtrans, c->d_brick_hit, c->d_rank, c->d_tile_order, c->d_tile_curve, c->d_image, c->d_scene_depth, c->d_samples, c->d_zsamples, c->d_cellinfo, c->d_occmask, c->d_slab_rect};
+                   c->d_lightmap, c->d_cubequads, c->d_depthmap, c->d_occluders, c->d_mvtrans, c->d_brick_hit, c->d_rank, c->d_tile_order, c->d_tile_curve, c->d_image, c->d_scene_depth, c->d_samples, c->d_zsamples, c->d_cellinfo, c->d_occmask, c->d_slab_rect, c->d_mvbox[0], c->d_mvbox[1]};
     for (void* p : dev) if (p) (void)hipFree(p);
     mesh_free_all(c);
     device_emitters_orphan_all(c);
@@ -536,6 +537,7 @@ VP_EXPORT int vp_fill(vp_ctx* c, const vp_fill_params* p)
     if (c->multi) return multi_fill(c, p);
     int rc = check_fill_ready(c, "vp_fill"); if (rc) return rc;
     if ((rc = ensure_device(c)) || (rc = stage_fill_inputs(c, p)) || (rc = ensure_bricks(c, false))) return rc;
+    mvbox_commit(c);
     rc = launch_fill(c, 0, nullptr, c->d_lightmap); if (rc) return rc;
     c->filled = true;
     return VP_OK;
@@ -558,6 +560,7 @@ VP_EXPORT int vp_fill_begin(vp_ctx* c, const vp_fill_params* p)
     c->bricks_grey = grey;
     // GL.Clear(false, true, Color.red) on lightPropogationTex: 1.0 in the R channel                       VPR.cs:498-499
     rc = launch_fill_value(c, c->d_lightmap, lightmap_elems(c), 1.0f); if (rc) return rc;
+    rc = mvbox_begin_per_mv(c); if (rc) return rc;
     c->fill_begun = true;
     c->filled = false;
     return VP_OK;
@@ -573,6 +576,7 @@ VP_EXPORT int vp_fill_metavoxel(vp_ctx* c, int32_t xx, int32_t yy, int32_t zz)
     if (zz < g.z0 || zz >= g.z1) return vp_fail(c, VP_ERR_BAD_ARG, "metavoxel slice %d is outside the owned slab [%d,%d)", zz, g.z0, g.z1);
     int rc = ensure_device(c); if (rc) return rc;
     rc = launch_fill_one(c, xx, yy, zz); if (rc) return rc;      // empty MV: the kernel skips it (VPR.cs:511)
+    rc = mvbox_commit_one(c, ((size_t)zz * g.Ny + yy) * g.Nx + xx); if (rc) return rc;
     c->filled = true;
     return VP_OK;
 }
@@ -641,6 +645,7 @@ VP_EXPORT int vp_fill_local(vp_ctx* c, const vp_fill_params* p, void* d_tau_out)
     VP_NO_FANOUT(c, "vp_fill_local");
     int rc = check_fill_ready(c, "vp_fill_local"); if (rc) return rc;
     if ((rc = ensure_device(c)) || (rc = stage_fill_inputs(c, p)) || (rc = ensure_bricks(c, true))) return rc;
+    mvbox_commit(c);
     rc = launch_fill(c, 1, nullptr, (float*)d_tau_out); if (rc) return rc;
     c->local_done = true;
     c->filled = false;

@@ -5,13 +5,15 @@
 //   k_bin<COUNT>   32 threads per particle, one candidate metavoxel each: candidate range + exact sphere/bordered-box test, atomic count
 //   k_scan_*       two-launch tiled exclusive scan: CSR offsets, brick slots (z-major = draw order), totals
 //   k_bin<SCATTER> same walk, atomic cursor -> unsorted CSR lists
-//   k_sort_lists   per occupied MV: rank sort -> ascending particle index (the reference's list order, :452)
+//   k_sort_lists   per occupied MV: rank sort -> ascending particle index (the reference's list order, :452); its trailing workgroups
+//                  form the metavoxels' voxel boxes (mv_box.h) for the ray-march
 //   k_col_ordinal  per occupied MV: how many occupied MVs of its column lie in front of it (chained fill, fill.hip)
 //
 // The reference clears N^3 managed lists and rebuilds a 4x4 inverse per candidate on the CPU; here the bins
 // are a CSR over an occupied-brick list and the per-MV inverse collapses to one shared 3x3 (rowsb) plus a
 // per-MV translation.  All acceptance arithmetic follows DESIGN.md section 4 exactly (bit-identical lists).
 #include "vpfx_internal.h"
+#include "mv_box.h"
 
 #include <chrono>
 
@@ -241,7 +243,7 @@ __device__ __forceinline__ void publish_totals(DevMeta* host_meta, const DevMeta
 __global__ void __launch_bounds__(SCAN_TILE)
 k_scan_write(const int* __restrict__ count, int n3, int nxy, int z0, int z1, const TileTotals* __restrict__ totals, int ntiles,
              int prefixed, int* __restrict__ offsets, int* __restrict__ brick_index, int* __restrict__ occ_list, int* __restrict__ cursor,
-             DevMeta* __restrict__ meta, DevMeta* __restrict__ host_meta, int seq)
+             DevMeta* __restrict__ meta, DevMeta* __restrict__ host_meta, int seq, uint2* __restrict__ mvbox)
 {
     __shared__ long long sh[48];
     __shared__ long long s_base[3];
@@ -276,6 +278,7 @@ k_scan_write(const int* __restrict__ count, int n3, int nxy, int z0, int z1, con
         const int slot = base_occ + b - (occ ? 1 : 0);
         brick_index[i] = occ ? slot : -1;
         if (occ) occ_list[slot] = i;
+        else mvbox[i] = make_uint2(VPFX_MVBOX_EMPTY_X, VPFX_MVBOX_EMPTY_Y);   // (an occupied cell's box: k_sort_lists)
     }
     if ((int)blockIdx.x == ntiles - 1 && threadIdx.x == SCAN_TILE - 1) {
         const long long total = base_pairs + a;
@@ -291,7 +294,7 @@ k_scan_write(const int* __restrict__ count, int n3, int nxy, int z0, int z1, con
 __global__ void __launch_bounds__(SCAN_TILE)
 k_scan_small(const int* __restrict__ count, int n3, int nxy, int z0, int z1, int* __restrict__ offsets, int* __restrict__ brick_index,
              int* __restrict__ occ_list, int* __restrict__ cursor, int* __restrict__ ord, int* __restrict__ colcount,
-             DevMeta* __restrict__ meta, DevMeta* __restrict__ host_meta, int seq)
+             DevMeta* __restrict__ meta, DevMeta* __restrict__ host_meta, int seq, uint2* __restrict__ mvbox)
 {
     __shared__ long long sh[48];
     __shared__ unsigned char s_occ[SCAN_TILE];
@@ -314,7 +317,7 @@ k_scan_small(const int* __restrict__ count, int n3, int nxy, int z0, int z1, int
             int n = 0;
             for (int z = z0; z < zz; ++z) n += s_occ[z * nxy + col];
             ord[i] = n;                                                     // position among the column's occupied metavoxels (k_col_ordinal)
-        }
+        } else mvbox[i] = make_uint2(VPFX_MVBOX_EMPTY_X, VPFX_MVBOX_EMPTY_Y);  // (an occupied cell's box: k_sort_lists)
         if (i < nxy) {
             int n = 0;
             for (int z = z0; z < z1; ++z) n += s_occ[z * nxy + i];
@@ -329,17 +332,66 @@ k_scan_small(const int* __restrict__ count, int n3, int nxy, int z0, int z1, int
     }
 }
 
-// Rank sort of one MV's list (ids are unique within a list).  One workgroup per occupied MV.
+// The voxel boxes of the occupied metavoxels (mv_box.h) for the ray-march: the union, over a metavoxel's list, of each particle's box.  Run by
+// the LEADING workgroups of k_sort_lists (their chain of loads is the longer one: dispatched last they would be the launch's tail), one wave
+// per metavoxel, four per workgroup: the list order does not matter to a union, so the
+// unsorted lists are read beside the workgroups that sort them -- the launch is a chain of dependent loads per workgroup (slot -> offsets ->
+// list -> position), and more independent workgroups cost it next to nothing, where the same work at the end of every sorting workgroup
+// made each of them longer (measured at C3: k_sort_lists 11.0 -> 17.7 us).  The six bounds are reduced as three pairs of 16-bit
+// fields, all of them minima (an upper bound u as 255 - u): one packed minimum and one cross-lane exchange serve two fields.
+struct BoxConsts { float Rl[9]; float inv_sb; int nv; };
+typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void mv_boxes(const int* __restrict__ occ_list, const int* __restrict__ offsets, const int* __restrict__ in, int slot,
+                                         const float4* __restrict__ ws4, const float* __restrict__ mvPos, const BoxConsts& bc, uint2* __restrict__ mvbox)
+{
+    const int lane = threadIdx.x & 63;
+    const int mi = occ_list[slot];
+    const int off = offsets[mi], n = offsets[mi + 1] - off;
+    const float mvx = mvPos[3 * mi], mvy = mvPos[3 * mi + 1], mvz = mvPos[3 * mi + 2];
+    MvBox acc = mv_box_empty();
+    for (int i = lane; i < n; i += 64) {
+        const float4 w = ws4[in[off + i]];
+        MvBox b;
+        if (mv_box_of_particle(w.x, w.y, w.z, w.w, mvx, mvy, mvz, bc.Rl, bc.inv_sb, bc.nv, b)) mv_box_union(acc, b);
+    }
+    // fields in [0, 256]: lo as it is (255 = none), hi as 255 - hi (hi = -1, none, gives 256)
+    u16x2_t p0 = {(unsigned short)acc.lo[0], (unsigned short)acc.lo[1]}, p1 = {(unsigned short)acc.lo[2], (unsigned short)(255 - acc.hi[0])},
+            p2 = {(unsigned short)(255 - acc.hi[1]), (unsigned short)(255 - acc.hi[2])};
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        p0 = __builtin_elementwise_min(p0, __builtin_bit_cast(u16x2_t, __shfl_xor(__builtin_bit_cast(int, p0), o)));
+        p1 = __builtin_elementwise_min(p1, __builtin_bit_cast(u16x2_t, __shfl_xor(__builtin_bit_cast(int, p1), o)));
+        p2 = __builtin_elementwise_min(p2, __builtin_bit_cast(u16x2_t, __shfl_xor(__builtin_bit_cast(int, p2), o)));
+    }
+    if (lane == 0) {
+        const MvBox u{{(int)p0[0], (int)p0[1], (int)p1[0]}, {255 - (int)p1[1], 255 - (int)p2[0], 255 - (int)p2[1]}};
+        uint32_t x, y;
+        mv_box_pack(u, x, y);
+        mvbox[mi] = make_uint2(x, y);
+    }
+}
+
+// Rank sort of one MV's list (ids are unique within a list).  One workgroup per occupied MV: workgroups [nbox, nbox + nsort); the nbox =
+// ceil(nsort / 4) workgroups in front of them form the voxel boxes, four metavoxels each (mv_boxes).
 #define SORT_CAP 4096
 __global__ void __launch_bounds__(256)
 k_sort_lists(const int* __restrict__ occ_list, const int* __restrict__ offsets, const int* __restrict__ in,
-             int* __restrict__ out, DevMeta* __restrict__ meta, int ahead_cap)
+             int* __restrict__ out, DevMeta* __restrict__ meta, int ahead_cap, int nsort, const float4* __restrict__ ws4,
+             const float* __restrict__ mvPos, BoxConsts bc, uint2* __restrict__ mvbox)
 {
     __shared__ int s_ids[SORT_CAP];
+    const int nbox = (nsort + 3) >> 2, sorter = (int)blockIdx.x - nbox;
+    if (sorter < 0) {
+        const int slot = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+        if (ahead_cap >= 0 ? (slot >= meta->occupied || (unsigned)meta->pairs > (unsigned)ahead_cap) : slot >= nsort) return;
+        mv_boxes(occ_list, offsets, in, slot, ws4, mvPos, bc, mvbox);
+        return;
+    }
     // launched ahead of the host's look at the totals (ahead_cap >= 0): one workgroup per metavoxel of the grid, those past the occupied
     // count leave; nothing runs if the lists do not fit the pool
-    if (ahead_cap >= 0 && ((int)blockIdx.x >= meta->occupied || (unsigned)meta->pairs > (unsigned)ahead_cap)) return;
-    const int mi = occ_list[blockIdx.x];
+    if (ahead_cap >= 0 && (sorter >= meta->occupied || (unsigned)meta->pairs > (unsigned)ahead_cap)) return;
+    const int mi = occ_list[sorter];
     const int off = offsets[mi], n = offsets[mi + 1] - off;
     if (n > SORT_CAP) {      // pathological list (> 4096 particles in one MV): the same rank sort straight from global memory
         for (int i = threadIdx.x; i < n; i += 256) {
@@ -416,11 +468,20 @@ int launch_bin(vp_ctx* c)
                            (const int*)nullptr, (int*)nullptr, c->d_rec, (const DevMeta*)nullptr, 0);
     }
     const bool small = n3 <= SCAN_TILE;
+    // the voxel boxes of this bin go into the buffer the ray-march is NOT reading; the next fill of the whole grid makes them current
+    // (mvbox_commit): bricks and boxes always come from the same bin
+    for (int i = 0; i < 2; ++i)
+        if (!c->d_mvbox[i]) VP_HIP(hipMalloc((void**)&c->d_mvbox[i], c->n3 * sizeof(uint2)));
+    uint2* box = c->d_mvbox[c->mvbox_cur ^ 1];
+    c->mvbox_fresh = true;
+    BoxConsts bc;
+    for (int i = 0; i < 9; ++i) bc.Rl[i] = g.Rl[i];
+    bc.inv_sb = g.inv_sb; bc.nv = g.nv;
     const int seq = ++c->bin_seq;                           // this frame's tag of the totals in pinned host memory (never 0 = the initial value)
     if (c->bin_seq == 0x7fffffff) c->bin_seq = 0;
     if (small) {
         hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(SCAN_TILE), 0, c->stream, c->d_count, n3, nxy, g.z0, g.z1, c->d_offsets, c->d_brick_index,
-                           c->d_occ_list, c->d_cursor, c->d_ord, c->d_colcount, c->d_meta, c->d_meta_host, seq);
+                           c->d_occ_list, c->d_cursor, c->d_ord, c->d_colcount, c->d_meta, c->d_meta_host, seq, box);
     } else {
         const int ntiles = (n3 + SCAN_TILE - 1) / SCAN_TILE;
         hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(SCAN_TILE), 0, c->stream, c->d_count, n3, nxy, g.z0, g.z1,
@@ -429,7 +490,7 @@ int launch_bin(vp_ctx* c)
         if (prefixed) hipLaunchKernelGGL(k_scan_prefix, dim3(1), dim3(SCAN_TILE), 0, c->stream, (TileTotals*)c->d_scan_totals, ntiles);
         hipLaunchKernelGGL(k_scan_write, dim3(ntiles), dim3(SCAN_TILE), 0, c->stream, c->d_count, n3, nxy, g.z0, g.z1,
                            (const TileTotals*)c->d_scan_totals, ntiles, prefixed, c->d_offsets, c->d_brick_index, c->d_occ_list, c->d_cursor, c->d_meta,
-                           c->d_meta_host, seq);
+                           c->d_meta_host, seq, box);
         hipLaunchKernelGGL(k_col_ordinal, dim3((nxy + 3) / 4), dim3(256), 0, c->stream, c->d_brick_index, nxy, g.z0, g.z1, c->d_ord, c->d_colcount);
     }
     // The totals are needed on the host to size the pair and brick pools.  While the host waits for them the GPU already fills the lists
@@ -442,8 +503,8 @@ int launch_bin(vp_ctx* c)
         hipLaunchKernelGGL(k_bin<1>, dim3(nb), dim3(256), 0, c->stream, c->d_ws, c->P, g, c->d_mvPos, c->d_cursor,
                            (const int*)c->d_offsets, c->d_ids_tmp, c->d_rec, (const DevMeta*)c->d_meta, ahead_cap);
         if (ahead_sort)
-            hipLaunchKernelGGL(k_sort_lists, dim3(n3), dim3(256), 0, c->stream, c->d_occ_list, c->d_offsets,
-                               (const int*)c->d_ids_tmp, c->d_ids, c->d_meta, ahead_cap);
+            hipLaunchKernelGGL(k_sort_lists, dim3(n3 + (n3 + 3) / 4), dim3(256), 0, c->stream, c->d_occ_list, c->d_offsets,
+                               (const int*)c->d_ids_tmp, c->d_ids, c->d_meta, ahead_cap, n3, (const float4*)c->d_ws, (const float*)c->d_mvPos, bc, box);
     }
     VP_HIP(hipGetLastError());
     // wait for the TOTALS, not for the stream: poll the sequence word the scan writes behind them.  The stream is asked now and then (a failed
@@ -482,11 +543,47 @@ int launch_bin(vp_ctx* c)
             hipLaunchKernelGGL(k_bin<1>, dim3(nb), dim3(256), 0, c->stream, c->d_ws, c->P, g, c->d_mvPos, c->d_cursor,
                                (const int*)c->d_offsets, c->d_ids_tmp, c->d_rec, (const DevMeta*)nullptr, 0);
         if (!sorted)
-            hipLaunchKernelGGL(k_sort_lists, dim3(c->h_meta.occupied), dim3(256), 0, c->stream, c->d_occ_list, c->d_offsets,
-                               (const int*)c->d_ids_tmp, c->d_ids, c->d_meta, -1);
+            hipLaunchKernelGGL(k_sort_lists, dim3(c->h_meta.occupied + (c->h_meta.occupied + 3) / 4), dim3(256), 0, c->stream, c->d_occ_list,
+                               c->d_offsets, (const int*)c->d_ids_tmp, c->d_ids, c->d_meta, -1, c->h_meta.occupied, (const float4*)c->d_ws,
+                               (const float*)c->d_mvPos, bc, box);
         VP_HIP(hipGetLastError());
     }
     VP_HIP(hipEventRecord(c->ev[0][1], c->stream));
     c->ev_valid[0] = true;
+    return VP_OK;
+}
+
+// ---- which bin's voxel boxes the ray-march reads (vp_ctx::d_mvbox) -------------------------------------------------------------------------
+namespace {
+__global__ void __launch_bounds__(256)
+k_mvbox_set(uint2* __restrict__ box, int n, uint2 v)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) box[i] = v;
+}
+}  // namespace
+
+void mvbox_commit(vp_ctx* c)
+{
+    if (!c->mvbox_fresh) return;                       // a second fill of the same bin: its boxes are current already
+    c->mvbox_cur ^= 1;
+    c->mvbox_fresh = false;
+}
+
+// The per-metavoxel fill rewrites the bricks it is called for and leaves the others as an earlier fill -- of an earlier bin -- left them.  A
+// brick of unknown content gets the box that clips nothing; vp_fill_metavoxel then hands each refilled cell its box of the last bin.
+int mvbox_begin_per_mv(vp_ctx* c)
+{
+    if (!c->mvbox_fresh) return VP_OK;                 // bricks and current boxes are of the same bin
+    hipLaunchKernelGGL(k_mvbox_set, dim3((unsigned)((c->n3 + 255) / 256)), dim3(256), 0, c->stream, c->d_mvbox[c->mvbox_cur], (int)c->n3,
+                       make_uint2(VPFX_MVBOX_FULL_X, VPFX_MVBOX_FULL_Y));
+    VP_HIP(hipGetLastError());
+    return VP_OK;
+}
+
+int mvbox_commit_one(vp_ctx* c, size_t mi)
+{
+    if (!c->mvbox_fresh) return VP_OK;
+    VP_HIP(hipMemcpyAsync(c->d_mvbox[c->mvbox_cur] + mi, c->d_mvbox[c->mvbox_cur ^ 1] + mi, sizeof(uint2), hipMemcpyDeviceToDevice, c->stream));
     return VP_OK;
 }

@@ -208,6 +208,8 @@ void hl_build_rm_consts(const vp_ctx* c, const vp_camera* cam, const vp_raymarch
     k->texBias = (float)g.b - 0.5f;
     k->inv_soft = 1.0f / (float)rp->soft_distance;                           // rcp(_SoftDistance)       RM.shader:269
     k->alpha_cutoff = 0.0f;
+    k->box_clip = 0;                                                         // decided per launch (launch_raymarch / launch_raymarch_one)
+    k->inv_step_tex = 1.0f / (k->mvStep * k->texScale);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

@@ -803,6 +803,7 @@ int multi_fill(vp_ctx* P, const vp_fill_params* p)
         c->filled = false;
         // (the previous frame's all-gather read this rank's slot of d_tau_all on the exchange stream: over before the fill below rewrites it)
         { const int rf = comm_fence(k); if (rf) return rf; }
+        mvbox_commit(c);
         if (fused) {
             r = launch_fill(c, 0, nullptr, c->d_lightmap);
             if (!r && hipMemcpyAsync(k.d_tau_all, c->d_lightmap, M->lm * sizeof(float), hipMemcpyDeviceToDevice, k.stream) != hipSuccess)

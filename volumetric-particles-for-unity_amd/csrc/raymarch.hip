@@ -239,6 +239,9 @@ int launch_raymarch(vp_ctx* c, const RmConsts& k_in, float* d_over, float* d_und
     const bool skip = k.occ_lds && k.Nz <= VPFX_RM_SKIP_RECTS && !(k.flags & ~VP_RM_NO_EARLY_OUT) &&
                       (c->rm_space_skip > 0 || (c->rm_space_skip == 0 && waves > (long long)c->num_cus * 8));
     if (skip) k.occ_lds |= 2;
+    // voxel-box clip of every visit (march_mv): the kernels without flag paths (the debug views keep the literal path), bricks with a border
+    // (a border-less brick's footprint wraps to the opposite face), boxes that fit their byte fields
+    k.box_clip = (c->rm_box_clip >= 0 && !(k.flags & ~VP_RM_NO_EARLY_OUT) && c->g.b >= 1 && k.nv <= 128 && k.texScale > 0.f && c->d_mvbox[c->mvbox_cur]) ? 1 : 0;
     const RmHandoff ho = (handoff && d_under) ? *handoff : RmHandoff{};          // slab (partial-image) kernels only
     const int early_out = (c->cfg.no_early_out == 1 || (k.flags & (VP_RM_NO_EARLY_OUT | VP_RM_SHOW_NUM_SAMPLES | VP_RM_SHOW_BLEND_FUNC | VP_RM_SHOW_DRAW_ORDER))) ? 0 : 1;
     k.flags &= ~VP_RM_NO_EARLY_OUT;                     // a launch switch, not a path of the FLAGS kernels

@@ -79,6 +79,22 @@ extern "C" __attribute__((visibility("default"))) int vpfx_rm_probe_read(unsigne
 #define VPFX_RM_PROF_PASS
 #define VPFX_RM_PROF_DUMMY
 #endif
+#if VPFX_RM_PROBE == 10
+// counting build of the voxel-box clip (measurement only, `make EXTRA=-DVPFX_RM_PROBE=10`): [0] lattice samples of all visits (early-out as
+// launched), [1] those the clip skipped, [2] visits, [3] visits left without a sample.  Read and reset through vpfx_rm_clip_read.
+#ifndef VPFX_RM_MAIN_TU
+static __device__ unsigned long long g_rm_clip[4];
+#else
+__device__ unsigned long long g_rm_clip[4];
+extern "C" __attribute__((visibility("default"))) int vpfx_rm_clip_read(unsigned long long* out, int reset)
+{
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rm_clip), 4 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    const unsigned long long z[4] = {0, 0, 0, 0};
+    if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_rm_clip), z, sizeof(z)) != hipSuccess) return -1;
+    return 0;
+}
+#endif
+#endif
 #ifndef VPFX_RM_SPI
 #define VPFX_RM_SPI 4          // lattice samples per loop iteration on grey bricks (see march_mv); 2 = rounds 2-3 (A/B, with VPFX_RM_WAVES_GREY=5)
 #endif
@@ -190,7 +206,7 @@ __device__ __forceinline__ RayCtx ray_setup(const RmConsts& k, int col, int row,
 // channels to filter.  Same image bit for bit as RGBA16F bricks.
 template <int NV, bool WRAP, bool FLAGS, bool GREY>
 __device__ __forceinline__ bool march_mv(const RmConsts& k, const RayCtx& R, const uint2* __restrict__ brick, const float4 tr,
-                                         F4& src, int& nsamp VPFX_RM_PROF_ARGS)
+                                         F4& src, int& nsamp, const uint2 box, const bool clip VPFX_RM_PROF_ARGS)
 {
     static_assert(!(WRAP && GREY), "grey bricks are only used with border >= 1 (the footprint never wraps)");
     const int nv = NV ? NV : k.nv;                   // NV = 0: run-time voxel count (raymarch_generic.hip)
@@ -312,6 +328,47 @@ __device__ __forceinline__ bool march_mv(const RmConsts& k, const RayCtx& R, con
     // so that eight texel-pair loads are in flight.
     const int tSoft = max(tEntry, min(tExit + 1, tCamera + k.soft));
     int si = tExit;
+    // The voxel box (mv_box.h; `clip`: launches without flag paths, border >= 1).  The fill leaves density exactly +0 in every texel outside
+    // the box, and the loops below start with rr = 0, trans = 1.  A sample whose eight texels all lie outside the box filters to density
+    // +0 (weights in [0, 1]), so bf = rcp(1.0) = 1.0, rr = fma(1, 0 - c, c) = +0, trans * 1 = trans, and the soft fade multiplies 0: the
+    // state after such a LEADING sample -- one marched before the ray has met the box, back to front -- equals the state before it bit for
+    // bit, and a visit without a sample left returns src = (0, 0, 0, 0), which blends into d as d exactly.  So the loops may start at the
+    // last lattice index whose footprint can meet the box.  (Trailing samples are not skipped: fl(fl(rr - c) + c) != rr in general.)
+    // Skip only: tExit, the sample count (ns, nsamp, brick_hit), the near end and the soft-fade bound stay what they were.
+    // Per axis the footprint [floor f, floor f + 1] meets [lo, hi] iff f in [lo - 1, hi + 1).  f(si) = fE + (si - tExit) fs with fE the
+    // texel at tExit (inside the cube: |fE| <= nv), so si - tExit lies between (lo - 1 - m - fE) / fs and (hi + 1 + m - fE) / fs;
+    // 1 / fs = R.id* * inv_step_tex.  The margin m = 1/16 texel covers the rounding of fE and of the loops' own f (half an ulp of 64 each),
+    // of 1 / fs (a few ulp: 4e-7 relative, times at most nv + 2 texels) and of the products: under 1e-4 texel together.  An axis the ray
+    // does not move along (1 / fs = +-inf) gives (-inf, +inf) inside the widened range and an empty interval outside it or on its edge
+    // (0 * inf = NaN, which fminf / fmaxf drop in favour of the other bound's infinity).
+    if (!WRAP && !FLAGS && clip) {
+        const float fsiE = (float)tExit, m1 = 1.0625f;
+        float first, last;
+        {
+            const float fE = fmaf(fsiE, fsx, f0x), iv = R.idx * k.inv_step_tex;
+            const float a = ((float)(box.x & 255u) - (fE + m1)) * iv, b = ((float)(box.y & 255u) - (fE - m1)) * iv;
+            first = fminf(a, b); last = fmaxf(a, b);
+        }
+        {
+            const float fE = fmaf(fsiE, fsy, f0y), iv = R.idy * k.inv_step_tex;
+            const float a = ((float)((box.x >> 8) & 255u) - (fE + m1)) * iv, b = ((float)((box.y >> 8) & 255u) - (fE - m1)) * iv;
+            first = fmaxf(first, fminf(a, b)); last = fminf(last, fmaxf(a, b));
+        }
+        {
+            const float fE = fmaf(fsiE, fsz, f0z), iv = R.idz * k.inv_step_tex;
+            const float a = ((float)((box.x >> 16) & 255u) - (fE + m1)) * iv, b = ((float)((box.y >> 16) & 255u) - (fE - m1)) * iv;
+            first = fmaxf(first, fminf(a, b)); last = fminf(last, fmaxf(a, b));
+        }
+        const int back = (int)floorf(fmaxf(fminf(last, 0.0f), -16777216.0f));              // <= 0: never past tExit
+        si = ((box.x >> 31) || first > last) ? tEntry - 1 : tExit + back;                   // no particle's voxel on the ray: no sample runs
+#if VPFX_RM_PROBE == 10
+        {
+            const int ns_all = max(0, tExit - tEntry + 1), cut = min(ns_all, tExit - si);
+            atomicAdd(&g_rm_clip[0], (unsigned long long)ns_all); atomicAdd(&g_rm_clip[1], (unsigned long long)cut);
+            atomicAdd(&g_rm_clip[2], 1ull); atomicAdd(&g_rm_clip[3], (ns_all > 0 && cut == ns_all) ? 1ull : 0ull);
+        }
+#endif
+    }
     float fsi = (float)si;                              // the index as a float, stepped with adds (one conversion per metavoxel, not per sample)
     VPFX_RM_TICK(2);                                    // per-metavoxel set-up (box test, lattice range, texel lattice)
     // (Measured and dropped: issuing the next two samples' eight loads before filtering the current two -- two register sets, 8-16 loads
@@ -519,7 +576,7 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
            const int* __restrict__ rank, const float* __restrict__ scene_depth, float4* __restrict__ img_over, float4* __restrict__ img_under,
            unsigned long long* __restrict__ samples, int* __restrict__ brick_hit, const int* __restrict__ tile_order, int early_out,
            RmHandoff ho, const float4* __restrict__ cellinfo, const uint32_t* __restrict__ occmask, int order_len,
-           const uint32_t* __restrict__ slab_rect)
+           const uint32_t* __restrict__ slab_rect, const uint2* __restrict__ mvbox)
 {
     const int lane = threadIdx.x;
     // XCD-aware tile order: workgroup b lands on XCD b % 8 (observed dispatch order; used for speed only), and each XCD
@@ -582,7 +639,10 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
     // starts over (two live images cost 4 registers that the 5-waves/SIMD budget does not have)
     F4 dst{0.f, 0.f, 0.f, 0.f};                                                            // OnPreRender clear  VPR.cs:171
     bool storedA = false;
-    const size_t pi = (size_t)row * k.W + col;
+    const size_t pi_ = (size_t)row * k.W + col;
+    // (the pixel index goes through an opaque copy at every use: the addresses formed from it -- image, hand-off maps -- are then computed where
+    // they are stored to instead of being held, two registers each, across the whole march)
+    auto pix = [&]() { size_t p = pi_; asm volatile("" : "+v"(p)); return p; };
     int nsamp = 0;
 
     // ray vs. the owned part of the grid
@@ -607,12 +667,15 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
     const int nxy = k.Nx * k.Ny;
     bool done = !(tg0 <= tg1);
     float tin = 1.0f, aA = 0.f;
-    const float cutoff = (PARTIAL && ho.t_in) ? VPFX_RM_HANDOFF_CUTOFF : k.alpha_cutoff;
+    // (a wave-uniform value: selected as an integer so that it lives in a scalar register -- as a float select it took a vector register
+    // across the slab loop, the one value the slab kernels spilled)
+    const int cutoff_bits = (PARTIAL && ho.t_in) ? 0x33000000 /* VPFX_RM_HANDOFF_CUTOFF */ : __float_as_int(k.alpha_cutoff);
+    auto cutoff_now = [&]() { return __int_as_float(cutoff_bits); };
     if (PARTIAL && ho.t_in) {
         int code = 0;                                          // product of the maps = sum of their codes (RmHandoff: t = 2^(-code / 8))
-        for (int j = 0; j < ho.n_in; ++j) code += ho.t_in[(size_t)j * ho.plane + pi];
+        for (int j = 0; j < ho.n_in; ++j) code += ho.t_in[(size_t)j * ho.plane + pix()];
         tin = __builtin_amdgcn_exp2f(-0.125f * (float)code);
-        if (early_out && tin <= cutoff) done = true;           // hidden by the slabs in front before this one starts
+        if (early_out && tin <= cutoff_now()) done = true;     // hidden by the slabs in front before this one starts
     }
 
     // Slab order.  The reference draws phase A (zz <= zBoundary) zz ascending, cells far -> near, blended OVER, then phase B
@@ -638,7 +701,7 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
         const bool phaseA = zz <= k.zB;                                                    // VPR.cs:667 vs :697
         const bool over = FLAGS && phaseA;                                                 // literal OVER, cells far -> near
         if (PARTIAL && !phaseA && !storedA) {
-            img_over[pi] = make_float4(dst.x, dst.y, dst.z, dst.w);
+            img_over[pix()] = make_float4(dst.x, dst.y, dst.z, dst.w);
             aA = dst.w;
             tin *= 1.0f - dst.w;                               // the slab's own phase-A image hides its phase-B image too
             dst = F4{0.f, 0.f, 0.f, 0.f};
@@ -689,6 +752,9 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
         // occupied cell turns up whose rank is below the last one marched, the order was not the ray's: the slab's blends are
         // rolled back (dst and the sample count as they were at the slab's start) and the slab is redone with selection by rank,
         // which the literal OVER order always uses.  (A separate look-ahead walk checking the ranks first cost 3.6 % of the kernel.)
+        // a cell's voxel box: base pointer + 32-bit byte offset (N^3 <= 2^28 cells of 8 bytes), the scalar-base form of the load -- no 64-bit
+        // address in vector registers
+        auto load_box = [&](int ci_) { return *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(mvbox) + ((unsigned)ci_ << 3)); };
         bool stream = !over;
         const F4 d_start = d;
         const int ns_start = nsamp;
@@ -700,6 +766,7 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
 #if VPFX_RM_CELLINFO
             float4 ci = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
 #endif
+            uint2 bx = make_uint2(0u, 0u);                      // the cell's voxel box (march_mv), loaded beside its record: no dependent trip
             if (stream) {
                 // next occupied cell along the ray
                 while (!wfin && walked < max_cells) {
@@ -712,10 +779,13 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
 #if VPFX_RM_OCC_LDS
                         if (k.occ_lds && !((s_occ[zz * k.Ny + ocy] >> ocx) & 1u)) continue;      // empty: no trip to memory
 #endif
-                        const float4 q4 = cellinfo[zz * nxy + cell];
+                        // (the record is the last of the three loads issued: the first use -- its slot -- then waits for all of them at once)
                         const int r = rank[cell];
+                        uint2 qb = make_uint2(0u, 0u);
+                        if (!WRAP && k.box_clip) qb = load_box(zz * nxy + cell);
+                        const float4 q4 = cellinfo[zz * nxy + cell];
                         if (__float_as_int(q4.w) >= 0) {
-                            if (r > last) { best_r = r; best_cell = cell; ci = q4; }
+                            if (r > last) { best_r = r; best_cell = cell; ci = q4; bx = qb; }
                             else { d = d_start; nsamp = ns_start; stream = false; last = -1; }
                             break;
                         }
@@ -746,6 +816,7 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
             }
             if (best_cell < 0) break;
             last = best_r;
+            if (!FLAGS && !WRAP && !stream && k.box_clip) bx = load_box(zz * nxy + best_cell);     // (selection by rank: the cell is only known now)
 #if VPFX_RM_CELLINFO
             const bool have_ci = !FLAGS && stream;
             const int bi = have_ci ? __float_as_int(ci.w) : occ[best_cell];
@@ -758,7 +829,7 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
             const int ns0 = nsamp;
             const uint2* brick = bricks + (size_t)bi * (NV ? NV * NV * NV : k.nv * k.nv * k.nv);
             VPFX_RM_TICK(1);                                   // cell walk: the next occupied metavoxel along the ray
-            if (!march_mv<NV, WRAP, FLAGS, GREY>(k, R, brick, trv, src, nsamp VPFX_RM_PROF_PASS)) { VPFX_RM_TICK(2); continue; }
+            if (!march_mv<NV, WRAP, FLAGS, GREY>(k, R, brick, trv, src, nsamp, bx, k.box_clip != 0 VPFX_RM_PROF_PASS)) { VPFX_RM_TICK(2); continue; }
             if (nsamp != ns0) brick_hit[bi] = 1;
             if (FLAGS && (k.flags & VP_RM_SHOW_BLEND_FUNC)) // debug view: yellow = OVER, cyan = UNDER   RM.shader:174-181
                 src = phaseA ? F4{0.5f, 0.5f, 0.f, 1.f} : F4{0.f, 0.5f, 0.5f, 1.f};
@@ -781,7 +852,7 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
         // also hides the slab's own phase-B image, which is composited behind it.)
         dst = d;
         if (PARTIAL) {
-            if (!over && early_out && (1.0f - d.w) * tin <= cutoff) done = true;
+            if (!over && early_out && (1.0f - d.w) * tin <= cutoff_now()) done = true;
             if (ho.zsamples && nsamp != ns_start)               // uniform address: hipcc reduces over the wave, one atomic per wave and slice
                 atomicAdd(ho.zsamples + (blockIdx.x & (VPFX_ZPROF_COPIES - 1)) * k.Nz + zz, (unsigned)(nsamp - ns_start));
         } else if (!over && early_out && 1.0f - d.w <= k.alpha_cutoff) done = true;
@@ -789,18 +860,18 @@ k_raymarch(RmConsts k, const int* __restrict__ brick_index, const uint2* __restr
 
     if (FLAGS && (k.flags & VP_RM_SHOW_RAY_SAMPLES)) dst = F4{(float)nsamp, (float)nsamp, (float)nsamp, 1.0f};   // perf view: samples per ray
     if (PARTIAL && storedA) {
-        img_under[pi] = make_float4(dst.x, dst.y, dst.z, dst.w);
+        img_under[pix()] = make_float4(dst.x, dst.y, dst.z, dst.w);
     } else {
-        img_over[pi] = make_float4(dst.x, dst.y, dst.z, dst.w);
-        if (PARTIAL) img_under[pi] = make_float4(0.f, 0.f, 0.f, 0.f);
+        img_over[pix()] = make_float4(dst.x, dst.y, dst.z, dst.w);
+        if (PARTIAL) img_under[pix()] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     if (PARTIAL && ho.t_out0) {
         // code = floor(-8 log2 t), capped at 255: the decoded 2^(-code / 8) is never below t (a conservative bound: it can only make a
         // ray behind march a little longer, never stop it early), within a factor 2^(1/8) of it down to 2^-31.9
         auto encode = [](float t) { return (uint8_t)(int)fminf(-8.0f * __builtin_amdgcn_logf(t), 255.0f); };
         const float t0 = storedA ? 1.0f - aA : 1.0f - dst.w;
-        ho.t_out0[pi] = encode(t0);
-        if (ho.t_out1) ho.t_out1[pi] = encode(storedA ? t0 * (1.0f - dst.w) : t0);
+        ho.t_out0[pix()] = encode(t0);
+        if (ho.t_out1) ho.t_out1[pix()] = encode(storedA ? t0 * (1.0f - dst.w) : t0);
     }
     if (nsamp) atomicAdd(samples, (unsigned long long)nsamp);
 #if VPFX_RM_PROBE == 9
@@ -1111,7 +1182,7 @@ k_raymarch_flat(RmConsts k, const int* __restrict__ brick_index, const uint2* __
                 F4 src;
                 const int nsb = nsamp;
                 VPFX_RM_PROF_DUMMY
-                if (!march_mv<NV, false, false, GREY>(k, R, bricks + (size_t)bi * NV * NV * NV, mvtrans[bi], src, nsamp VPFX_RM_PROF_PASS)) continue;
+                if (!march_mv<NV, false, false, GREY>(k, R, bricks + (size_t)bi * NV * NV * NV, mvtrans[bi], src, nsamp, make_uint2(0u, 0u), false VPFX_RM_PROF_PASS)) continue;
                 if (nsamp != nsb) brick_hit[bi] = 1;
                 const float ia = 1.0f - dst.w;
                 dst.x = src.x * ia + dst.x; dst.y = src.y * ia + dst.y; dst.z = src.z * ia + dst.z; dst.w = src.w * ia + dst.w;
@@ -1153,7 +1224,7 @@ k_raymarch_one(RmConsts k, const uint2* __restrict__ brick, float4 tr, const flo
     F4 src;
     int nsamp = 0;
     VPFX_RM_PROF_DUMMY
-    if (!march_mv<NV, WRAP, true, GREY>(k, R, brick, tr, src, nsamp VPFX_RM_PROF_PASS)) return;  // no fragment: the ROP is not touched
+    if (!march_mv<NV, WRAP, true, GREY>(k, R, brick, tr, src, nsamp, make_uint2(0u, 0u), false VPFX_RM_PROF_PASS)) return;  // no fragment: the ROP is not touched
     if (k.flags & VP_RM_SHOW_BLEND_FUNC) src = blend_over ? F4{0.5f, 0.5f, 0.f, 1.f} : F4{0.f, 0.5f, 0.5f, 1.f};
     if (k.flags & VP_RM_SHOW_DRAW_ORDER) src = draw_order_color(order_index, k.num_covered);
     const size_t pi = (size_t)row * k.W + col;
@@ -1214,7 +1285,8 @@ void launch_rm_variant(vp_ctx* c, const RmConsts& k, float* d_over, float* d_und
     const dim3 grid(((order_len + 7) / 8) * 8 * (4 << (VPFX_RM_LX + VPFX_RM_LY))), block(64);
     hipLaunchKernelGGL((k_raymarch<NV, PARTIAL, WRAP, FLAGS, GREY>), grid, block, 0, c->stream, k, c->d_brick_index, c->d_bricks, c->d_mvtrans,
                        c->d_rank, c->d_scene_depth, (float4*)d_over, (float4*)d_under, c->d_samples, c->d_brick_hit, order, early_out, ho,
-                       (const float4*)c->d_cellinfo, (const uint32_t*)c->d_occmask, order_len, (const uint32_t*)c->d_slab_rect);
+                       (const float4*)c->d_cellinfo, (const uint32_t*)c->d_occmask, order_len, (const uint32_t*)c->d_slab_rect,
+                       (const uint2*)c->d_mvbox[c->mvbox_cur]);
 }
 
 #if VPFX_AB

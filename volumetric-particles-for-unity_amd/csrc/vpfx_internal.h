@@ -81,6 +81,8 @@ struct RmConsts {
     float texScale, texBias;      // texel coordinate = local * (nv - 2b) + (b - 0.5)
     float inv_soft;
     float alpha_cutoff;           // early-out once (1 - dst.a) <= cutoff in the UNDER phase (0 = exact only)
+    int   box_clip;               // 1 = march_mv starts a visit at the metavoxel's voxel box (mv_box.h) instead of at the cube's far face; launch_raymarch
+    float inv_step_tex;           // 1 / (mvStep * texScale): lattice indices per texel along a unit direction component (the clip's slab solve)
 };
 // Empty-slab skipping of k_raymarch (raymarch.hip: slab_rect): d_slab_rect holds one packed word per light-axis slab, the rectangle of its
 // occupied cells; a ray skips the slabs whose rectangle its (x, y) range in the slab, widened by one cell, misses.  RmConsts.occ_lds carries
@@ -233,6 +235,13 @@ struct vp_ctx {
     uint32_t* d_slab_rect = nullptr; // [VPFX_RM_SKIP_RECTS] per-slab rectangle of the occupied cells (k_rm_prepare -> k_raymarch's LDS)
     uint32_t* d_occmask = nullptr; // [Nz][Ny] one bit per cell (Nx <= 32): occupied metavoxels, copied into LDS by k_raymarch for the cell walk
     float4* d_cellinfo = nullptr; // [N^3] (translation, brick slot | -1) per cell: VPFX_RM_CELLINFO A/B variant of the cell walk
+    // Per-cell voxel boxes (mv_box.h), indexed like d_cellinfo.  Two buffers: launch_bin writes the one the ray-march is not reading
+    // (mvbox_cur ^ 1) and the fill of the whole grid makes it current (mvbox_commit), so a ray-march always clips with the boxes of the bin
+    // its bricks were filled from.  The per-metavoxel fill commits cell by cell (mvbox_begin_per_mv / mvbox_commit_one).
+    uint2* d_mvbox[2] = {nullptr, nullptr};
+    int mvbox_cur = 0;
+    bool mvbox_fresh = false;     // the other buffer holds a bin that no whole-grid fill has made current yet
+    int rm_box_clip = 0;          // VPFX_RM_NO_BOX_CLIP in the environment at vp_create (test switch, A/B timing): -1 = never clip, 1 = clip in every launch, 0 = the default rule
     int* d_rank = nullptr;        // [Ny*Nx] draw-order rank of the (yy, xx) columns for this frame's camera (VPR.cs:613-632), written by k_rm_prepare
     int* d_tile_order = nullptr;  // [rm_order_ints + super-tiles] dispatch order of k_raymarch (most expensive first), then the float cost estimates
     float* d_image = nullptr;     // [H][W][4]
@@ -299,6 +308,9 @@ void   hl_fit_grid(const float l2w[16], const float lo[3], const float hi[3], co
 // bin.hip
 int  launch_extract(vp_ctx* c);
 int  launch_bin(vp_ctx* c);
+void mvbox_commit(vp_ctx* c);                          // a fill of the whole grid (fused or local pass) starts: the last bin's boxes become the ray-march's
+int  mvbox_begin_per_mv(vp_ctx* c);                    // vp_fill_begin: no brick of the last bin is filled yet -- every current box says "whole brick"
+int  mvbox_commit_one(vp_ctx* c, size_t mi);           // vp_fill_metavoxel: that cell's brick now comes from the last bin, and so does its box
 int  launch_z_histogram(vp_ctx* c, int* d_hist);
 // fill.hip
 int  launch_build_cubequads(vp_ctx* c, const void* d_cube, int format, int S, int* d_bad);
