@@ -1,4 +1,4 @@
-"""Independent float64 numpy restatement of the hot path, used ONLY to pin the C oracle.
+"""Independent float64 numpy restatement of the hot path, used to pin the C oracle and, in tests/test_gpu_twin.py, the HIP path itself.
 
 TEST INFRASTRUCTURE (parity unpinned, see vp_oracle.c).  Written from the reference's shader / C# text with a
 different structure than vp_oracle.c (vectorised per metavoxel, float64, literal `voxelWorldPos += fwd*one`
