@@ -44,7 +44,9 @@ extern "C" {
                                 6 (additive): particles that stay on the GPU -- vp_upload_particles_device, vp_device_emitter_*,
                                    vp_upload_particles_from_emitter, vp_emitter_schedule; detected by the presence of the symbols as well
                                 6 (additive): where the resident particles are and what the bin kept of them -- vp_particle_bounds,
-                                   vp_particle_coverage, vp_fit_grid (host only); detected by the presence of the symbols as well */
+                                   vp_particle_coverage, vp_fit_grid (host only); detected by the presence of the symbols as well
+                                6 (additive): volume shadows -- the light-propagation map projected onto the opaque scene: vp_shadow_params,
+                                   vp_volume_shadow_points / _image (+ _device forms), vp_apply_shadow_device; detected by the presence of the symbols */
 
 typedef enum vp_status {
     VP_OK = 0,
@@ -667,6 +669,56 @@ typedef struct vp_grid_fit {
 } vp_grid_fit;                    /* 64 bytes */
 int  vp_fit_grid(const float light_to_world[16], const float ls_min[3], const float ls_max[3], const int32_t num_mv[3],
                  float mv_scale, float snap, vp_grid_fit* out);
+
+/* ABI 6 (additive): volume shadows -- the shadow the particle volume casts on the opaque scene.
+ * The fill keeps, per light-map column, the light "prior to occlusion" so that "we can project the light propagation texture on to the scene
+ * ... and thus have shadows cast by the volume" (FillVolume.shader:224-250; bound at RayMarchVoxel.shader:4,43 and VPR.cs:719); the reference
+ * never does the projection.  These calls do it on the GPU, from the map of the most recent fill and the grid constants currently in effect
+ * (as the ray-march uses them): no brick is sampled, no read-back, no grid mapping redone in a host shader.
+ *
+ * The factor of a world point p (f32, no FMA, in this order):
+ *   ls_r = ((Linv(r,0) p.x + Linv(r,1) p.y) + Linv(r,2) p.z) + Linv(r,3)          Linv = the light's worldToLocal (vp_set_frame)
+ *   gx = ((ls.x - lsO.x) / s + (float)(Nx / 2)) + 0.5, likewise gy, gz             lsO = Linv * grid_center, s = mv_scale, INTEGER N / 2
+ *   inside = gx >= 0 && gx < Nx && gy >= 0 && gy < Ny && gz >= 0                   not inside (or not finite): factor 1
+ *   xx = floor(gx), u = gx - xx, tx = (u (nv - 2b) + b) - 0.5, likewise yy, ty     the ray-march's texel rule on the tile of column (xx, yy)
+ *   VP_SHADOW_NEAREST   f = Lm[yy nv + clamp(floor(ty + 0.5), 0, nv - 1)][xx nv + clamp(floor(tx + 0.5), 0, nv - 1)]
+ *   VP_SHADOW_BILINEAR  x0 = floor(tx), wx = tx - x0 (likewise y); x0, x0 + 1, y0, y0 + 1 clamped to [0, nv - 1] INSIDE the tile (its border
+ *                       texels are the neighbours' data, as the bricks are filtered; the clamp only acts when b = 0);
+ *                       a = L00 + wx (L10 - L00), c = L01 + wx (L11 - L01), f = a + wy (c - a)
+ *   factor = 1 - strength (1 - f); strength == 1: factor = f, the map's value to the bit (1 - (1 - f) would round an f below 0.5)
+ * A point outside the grid's footprint, or between the light and the grid's near face, gets 1; a point behind the far face is inside and
+ * takes the light that leaves the grid.
+ * The image form applies this to the surface point of every pixel: the pixel-centre ray of vp_render_scene_depth (row 0 = bottom of the view),
+ * p = cam origin + (d / -dz) dir for the linear eye depth d of that pixel; d >= 3e38 (nothing there) or not > 0 gives exactly 1.
+ *
+ *   - synchronisation: vp_volume_shadow_points / _image copy in, run, copy out and wait once on the context's stream.  The _device forms and
+ *     vp_apply_shadow_device take memory of the context's device, queue on the stream and never wait.
+ *   - scene_depth == NULL: the eye depth rendered from the context's solids and mesh instances -- the very map vp_raymarch uses, rendered once per
+ *     camera and occluder set.  With no occluders set the result is 1.0 everywhere.
+ *   - a caller-supplied scene_depth ([H][W] f32 linear eye depth) is staged in a buffer of its own: it does not disturb the kept rendered maps nor
+ *     the depth a later vp_raymarch uses.
+ *   - VP_ERR_STATE: no fill has completed (vp_fill, or vp_fill_begin plus the vp_fill_metavoxel calls).
+ *   - VP_ERR_UNSUPPORTED: a fan-out context; a context that owns only part of the light axis (slab_z0 / slab_z1: its map is not the whole
+ *     column's); n > 2^31 - 1.
+ *   - VP_ERR_BAD_ARG: a null pointer with n > 0, n < 0, a filter other than 0 / 1, a strength outside [0, 1] or not finite, non-zero reserved[],
+ *     a null camera, null params, a null output image.  n = 0 is valid.  A refused call writes nothing and changes nothing.
+ *   - vp_apply_shadow_device: scene.rgb *= shadow in place on [H][W][4] f32, alpha untouched -- in front of vp_composite_device.
+ *   - what the factor means: the light arriving at the surface the light depth map recorded in that column (the propagate loop stops at it), or
+ *     leaving the grid.  It is meant to scale the directional light on first-lit surfaces; it knows nothing of the scene's own shadows (a
+ *     surface that is not the first seen from the light is in the scene's shadow anyway).  LIMIT: the light depth map holds the nearest BACK
+ *     face (LDM.shader:6 Cull Front), so where particles poke into an occluder the factor includes their attenuation down to its back face. */
+#define VP_SHADOW_NEAREST  0
+#define VP_SHADOW_BILINEAR 1
+typedef struct vp_shadow_params {
+    int32_t filter;               /* VP_SHADOW_*                                                   */
+    float   strength;             /* 0 = no shadow .. 1 = the map's value                          */
+    int32_t reserved[2];          /* must be 0                                                     */
+} vp_shadow_params;               /* 16 bytes */
+int  vp_volume_shadow_points(vp_ctx* ctx, const float* world_xyz /* [n][3] */, int64_t n, const vp_shadow_params* params, float* out /* [n] */);
+int  vp_volume_shadow_points_device(vp_ctx* ctx, const void* d_world_xyz, int64_t n, const vp_shadow_params* params, void* d_out);
+int  vp_volume_shadow_image(vp_ctx* ctx, const vp_camera* cam, const float* scene_depth, const vp_shadow_params* params, float* out /* [H][W] */);
+int  vp_volume_shadow_image_device(vp_ctx* ctx, const vp_camera* cam, const void* d_scene_depth, const vp_shadow_params* params, void* d_out);
+int  vp_apply_shadow_device(vp_ctx* ctx, const void* d_shadow, void* d_scene_rgba);
 
 /* ---- parity probes / stats ------------------------------------------------------------------ */
 int  vp_get_mv_positions(vp_ctx* ctx, float* pos_out /* [Nz][Ny][Nx][3] */);

@@ -220,6 +220,14 @@ class vp_grid_fit(C.Structure):
                 ("min_mv_scale", C.c_float), ("fits", C.c_int32), ("clipped", C.c_int32), ("reserved", C.c_int32)]
 
 
+VP_SHADOW_NEAREST, VP_SHADOW_BILINEAR = 0, 1
+
+
+class vp_shadow_params(C.Structure):
+    """ABI 6 (additive): how the light-propagation map is sampled and how strong the volume's shadow is (vp_volume_shadow_*); 16 bytes."""
+    _fields_ = [("filter", C.c_int32), ("strength", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
 class vp_stats(C.Structure):
     _fields_ = [
         ("particles", C.c_int64),
@@ -269,6 +277,7 @@ EXPORTED_SYMBOLS = [
     "vp_upload_particles_device", "vp_device_emitter_create", "vp_device_emitter_destroy", "vp_device_emitter_step", "vp_device_emitter_count",
     "vp_device_emitter_read_particles", "vp_upload_particles_from_emitter", "vp_emitter_schedule",
     "vp_particle_bounds", "vp_particle_coverage", "vp_fit_grid",
+    "vp_volume_shadow_points", "vp_volume_shadow_points_device", "vp_volume_shadow_image", "vp_volume_shadow_image_device", "vp_apply_shadow_device",
 ]
 class vp_xop(C.Structure):
     """One operation of the image exchange's message schedule (vp_exchange_plan)."""

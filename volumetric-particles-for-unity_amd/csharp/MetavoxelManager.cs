@@ -20,6 +20,8 @@
 //   ZTest vs the scene depth     VPR.cs:204       -> the same solids (the library renders the eye depth), or _CameraDepthTexture read back
 //                                                    and passed as vp_raymarch_params.scene_depth
 //   composite + present          VPR.cs:210-219   -> Graphics.Blit(particlesTex, mainSceneRT, matBlendParticles); Blit to the back buffer
+// and what it adds: the volume's shadow on the opaque scene (castVolumeShadows) -- the projection of lightPropogationTex the reference planned
+// (FillVolume.shader:224-250) and never made: vp_volume_shadow_image, multiplied into mainSceneRT in front of the composite.
 using System;
 using System.Collections.Generic;
 using System.Runtime.InteropServices;
@@ -90,6 +92,10 @@ namespace MetavoxelEngine
         public int rebalanceInterval = 240;        // multi-GPU: frames between vp_rebalance calls (0 = never re-cut the slabs)
         public bool asyncReadback = false;         // vp_raymarch_async: the image is shown one frame late, its copy runs beside the next frame's fill
         public bool useRenderThread = false;       // run the frame from Unity's render thread (GL.IssuePluginEvent) instead of OnPostRender
+        public bool castVolumeShadows = false;     // CompositeParticles darkens mainSceneRT by the volume's shadow (vp_volume_shadow_image) before the blend
+        public float shadowStrength = 1.0f;        // vp_shadow_params.strength: 0 = none .. 1 = the light-propagation map's value
+        public int shadowFilter = 1;               // VP_SHADOW_NEAREST = 0, VP_SHADOW_BILINEAR = 1
+        public Material matMultiplyShadow;         // csharp/VpfxMultiplyShadow.shader (Blend DstColor Zero, ColorMask RGB)
 
         // ---- C ABI (include/vpfx.h) ---------------------------------------------------------------------
         [StructLayout(LayoutKind.Sequential)]
@@ -157,6 +163,13 @@ namespace MetavoxelEngine
         }
 
         [StructLayout(LayoutKind.Sequential)]
+        struct vp_shadow_params                // ABI 6 (additive): how the light-propagation map is sampled for the volume's shadow (16 bytes)
+        {
+            public int filter; public float strength;
+            public int reserved0, reserved1;   // must be 0
+        }
+
+        [StructLayout(LayoutKind.Sequential)]
         struct vp_unity_frame                  // one frame for the render-thread callback (include/vpfx.h "Unity native-plugin hookup")
         {
             public IntPtr ctx; public int flags, particle_count;
@@ -196,6 +209,8 @@ namespace MetavoxelEngine
         [DllImport(LIB)] static extern int vp_unity_clear_slot(int slot);
         [DllImport(LIB)] static extern int vp_unity_register_output_fd(int slot, IntPtr ctx, int fd, ulong bytes, ulong offset);   // texture interop: the exported render-texture memory
         [DllImport(LIB)] static extern int vp_particle_bounds(IntPtr ctx, float[] worldToFrame, out vp_particle_bounds bounds);   // null frame = world space
+        [DllImport(LIB)] static extern int vp_volume_shadow_image(IntPtr ctx, ref vp_camera cam, IntPtr sceneDepth, ref vp_shadow_params p, IntPtr shadowOut);   // sceneDepth NULL = the eye depth the library renders
+        [DllImport(LIB)] static extern int vp_volume_shadow_points(IntPtr ctx, float[] worldXyz, long n, ref vp_shadow_params p, float[] factorsOut);
         [DllImport(LIB)] static extern int vp_fit_grid(float[] lightToWorld, float[] lsMin, float[] lsMax, int[] numMv, float mvScale, float snap, out vp_grid_fit fit);
 
         IntPtr ctx = IntPtr.Zero;
@@ -218,6 +233,9 @@ namespace MetavoxelEngine
         Texture2D lightDepthTex, sceneDepthTex;
         int occluderHash = 0; bool occludersSent = false;
         int meshShapesHash = 0; bool meshShapesSent = false;   // AllSceneMeshes: the sharedMesh list the context holds
+        float[] shadow;                // castVolumeShadows: the factor image [H][W], row 0 = bottom (allocated by the first frame that needs it)
+        GCHandle shadowHandle;
+        Texture2D shadowTex;
 
         static float[] ToArray(Matrix4x4 m)   // Unity Matrix4x4 is column-major in memory: m00,m10,m20,m30,m01,...
         {
@@ -326,6 +344,7 @@ namespace MetavoxelEngine
             if (cubeHandle.IsAllocated) cubeHandle.Free();
             if (lightDepthHandle.IsAllocated) lightDepthHandle.Free();
             if (sceneDepthHandle.IsAllocated) sceneDepthHandle.Free();
+            if (shadowHandle.IsAllocated) shadowHandle.Free();
             vp_destroy(ctx); ctx = IntPtr.Zero;
         }
 
@@ -355,12 +374,46 @@ namespace MetavoxelEngine
         }
 
         // Blend the particles onto the opaque scene and present (VPR.cs:210, 216-219; CompositeParticles.shader:10 -- the reference's own material).
-        void CompositeParticles()
+        // contextIdle = false: a render-thread event may be running on the context, so no library call is made (the scene keeps last frame's look).
+        void CompositeParticles(bool contextIdle = true)
         {
             if (mainSceneRT == null) return;
+            if (castVolumeShadows && contextIdle && filledOnce && matMultiplyShadow != null) CastVolumeShadow();
             if (matBlendParticles != null) Graphics.Blit(particlesTex, mainSceneRT, matBlendParticles);
             GetComponent<Camera>().targetTexture = null;                   // else the Blit to the back buffer does not work (VPR.cs:218)
             Graphics.Blit(mainSceneRT, null as RenderTexture);
+        }
+
+        // The other half of the effect: the opaque scene under the smoke loses the light the volume took.  The factor image comes from the light-
+        // propagation map of the last fill and the same depth source as the ray-march (SceneDepthPtr: the read-back copy, or NULL = the eye depth the
+        // library renders from the solids it holds); mainSceneRT.rgb is multiplied by it in front of the composite.
+        void CastVolumeShadow()
+        {
+            if (shadow == null)
+            {
+                shadow = new float[Screen.width * Screen.height];
+                shadowHandle = GCHandle.Alloc(shadow, GCHandleType.Pinned);
+                shadowTex = new Texture2D(Screen.width, Screen.height, TextureFormat.RFloat, false);
+            }
+            vp_camera cam; vp_raymarch_params rp;
+            CameraAndParams(out cam, out rp);
+            var sp = new vp_shadow_params { filter = shadowFilter, strength = Mathf.Clamp01(shadowStrength), reserved0 = 0, reserved1 = 0 };
+            if (!Check(vp_volume_shadow_image(ctx, ref cam, SceneDepthPtr(), ref sp, shadowHandle.AddrOfPinnedObject()), "vp_volume_shadow_image")) return;
+            shadowTex.SetPixelData(shadow, 0);
+            shadowTex.Apply(false);
+            Graphics.Blit(shadowTex, mainSceneRT, matMultiplyShadow);
+        }
+
+        // The light a point in the world still gets through the volume (light probes, forward-lit objects): multiply the directional light by it.
+        public float[] VolumeShadowAt(Vector3[] worldPoints)
+        {
+            var xyz = new float[worldPoints.Length * 3];
+            for (int i = 0; i < worldPoints.Length; i++) { xyz[3 * i] = worldPoints[i].x; xyz[3 * i + 1] = worldPoints[i].y; xyz[3 * i + 2] = worldPoints[i].z; }
+            var factors = new float[worldPoints.Length];
+            var sp = new vp_shadow_params { filter = shadowFilter, strength = Mathf.Clamp01(shadowStrength), reserved0 = 0, reserved1 = 0 };
+            if (!filledOnce || !Check(vp_volume_shadow_points(ctx, xyz, (long)worldPoints.Length, ref sp, factors), "vp_volume_shadow_points"))
+                for (int i = 0; i < factors.Length; i++) factors[i] = 1.0f;
+            return factors;
         }
 
         // The opaque scene as the library sees it.  SceneMeshes: collect the Default-layer primitives and hand them over when something moved.
@@ -497,7 +550,7 @@ namespace MetavoxelEngine
             // completion handshake: the event issued last frame reads `parts` (vp_bin) and writes `rgba` (read-back) whenever the render thread
             // gets to it.  Until the library has counted it (events_run == issued) neither array may be touched and nothing else may run on the
             // context: skip this frame's issue and show the previous texture.
-            if (done < issuedEvents) { CompositeParticles(); return; }      // still present the opaque scene + the previous particles
+            if (done < issuedEvents) { CompositeParticles(false); return; }      // still present the opaque scene + the previous particles
             if (done > 0) { Check(last, "render-thread frame"); if (last == 0) { filledOnce = true; cubemapResident = true; particlesTex.SetPixelData(rgba, 0); particlesTex.Apply(false); } }
             if (gpuDevices.Length > 1 && rebalanceInterval > 0 && Time.frameCount % rebalanceInterval == 0) vp_rebalance(ctx);   // no event in flight here
             SyncOccluders();                                               // likewise: the context is idle between events
@@ -669,5 +722,7 @@ namespace MetavoxelEngine
         public void SetUpdateInterval(float v) { updateInterval = Mathf.Max(1, (int)v); }
         public void SetFadeOutParticles(bool v) { fadeOutParticles = v; }
         public void SetShowMetavoxelDrawOrder(bool show) { bShowMetavoxelDrawOrder = show; }   // VPR.cs:1096-1099
+        public void SetCastVolumeShadows(bool v) { castVolumeShadows = v; }                   // added by this binding
+        public void SetShadowStrength(float v) { shadowStrength = Mathf.Clamp01(v); }
     }
 }

@@ -209,6 +209,7 @@ int stage_raymarch(vp_ctx* c, const vp_camera* cam, const vp_raymarch_params* rp
 // the single-device building blocks the fan-out (multi.cpp) runs on its slab contexts
 int api_stream_sync(vp_ctx* c) { return stream_sync(c); }
 int api_stage_fill_inputs(vp_ctx* c, const vp_fill_params* p) { return stage_fill_inputs(c, p); }
+int api_ensure_eye_depth(vp_ctx* c, const vp_camera* cam) { return ensure_eye_depth(c, cam); }
 int api_ensure_bricks(vp_ctx* c, bool need_scratch) { return ensure_bricks(c, need_scratch); }
 int api_stage_raymarch(vp_ctx* c, const vp_camera* cam, const vp_raymarch_params* rp, RmConsts* k) { return stage_raymarch(c, cam, rp, k); }
 int api_set_slab(vp_ctx* c, int z0, int z1)
@@ -364,6 +365,7 @@ void vp_destroy_single(vp_ctx* c)
     mesh_free_all(c);
     device_emitters_orphan_all(c);
     particle_queries_free(c);
+    volume_shadow_free(c);
     if (c->h_chain_err) (void)hipHostFree(c->h_chain_err);
     if (c->h_meta_host) (void)hipHostFree(c->h_meta_host);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }

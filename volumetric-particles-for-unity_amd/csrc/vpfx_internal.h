@@ -227,6 +227,13 @@ struct vp_ctx {
     int* d_cover = nullptr;       // [cover_cap] metavoxel lists each particle is in (vp_particle_coverage)
     size_t cover_cap = 0;
 
+    // volume shadows (volume_shadow.hip): staging of the host forms, allocated by the first call that needs it; the frame path never sees them
+    float* d_shadow_depth = nullptr;    // [H][W] a caller's eye depth (never d_scene_depth: that one keeps the rendered map for the ray-march)
+    float* d_shadow_image = nullptr;    // [H][W] the factor image before its copy to the host
+    float* d_shadow_points = nullptr;   // [shadow_points_cap][3]
+    float* d_shadow_factors = nullptr;  // [shadow_points_cap]
+    size_t shadow_points_cap = 0;
+
     // raymarch
     float4* d_mvtrans = nullptr;  // [brick_cap] per-brick translation column of _CameraToMetavoxel
     size_t mvtrans_cap = 0;
@@ -351,6 +358,9 @@ int  api_upload_particles_from(vp_ctx* c, const UploadSource& src, int32_t count
 void device_emitters_orphan_all(vp_ctx* c);            // vp_destroy: free the device arrays of the context's emitters and detach them
 // particle_bounds.hip
 void particle_queries_free(vp_ctx* c);                 // vp_destroy: the scratch of vp_particle_bounds / vp_particle_coverage
+// volume_shadow.hip
+void volume_shadow_free(vp_ctx* c);                    // vp_destroy: the staging buffers of the vp_volume_shadow_* host forms
+int  api_ensure_eye_depth(vp_ctx* c, const vp_camera* cam);   // the eye depth rendered from the solids and mesh instances, in d_scene_depth (cached per camera)
 int  api_stage_fill_inputs(vp_ctx* c, const vp_fill_params* p);
 int  api_ensure_bricks(vp_ctx* c, bool need_scratch);
 int  api_stage_raymarch(vp_ctx* c, const vp_camera* cam, const vp_raymarch_params* rp, RmConsts* k);

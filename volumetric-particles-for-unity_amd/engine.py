@@ -72,6 +72,11 @@ def lib():
         L.vp_particle_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.vp_particle_coverage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.vp_fit_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
+        L.vp_volume_shadow_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.vp_volume_shadow_points_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.vp_volume_shadow_image.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_volume_shadow_image_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vp_apply_shadow_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -287,6 +292,44 @@ class Engine:
     def composite_device(self, d_particles: int, d_scene: int):
         self._ck(self.L.vp_composite_device(self.h, C.c_void_p(d_particles), C.c_void_p(d_scene)), "vp_composite_device")
 
+    # -- volume shadows: the light-propagation map of the last fill projected onto the opaque scene ------
+    def volume_shadow_points(self, world_xyz, filter=abi.VP_SHADOW_BILINEAR, strength=1.0):
+        """vp_volume_shadow_points: the factor in [0, 1] that scales the directional light at each world point [n, 3] (light probes,
+        forward-lit objects): 1 outside the grid's footprint and in front of it, the map's value in and behind it.  One wait on the stream."""
+        p = np.ascontiguousarray(world_xyz, dtype=np.float32).reshape(-1, 3)
+        out = np.empty(len(p), dtype=np.float32)
+        sp = shadow_params(filter, strength)
+        self._ck(self.L.vp_volume_shadow_points(self.h, _vp(p) if len(p) else None, C.c_int64(len(p)), C.byref(sp), _vp(out) if len(p) else None),
+                 "vp_volume_shadow_points")
+        return out
+
+    def volume_shadow_points_device(self, d_world_xyz: int, n: int, d_out: int, filter=abi.VP_SHADOW_BILINEAR, strength=1.0):
+        """The same on device memory ([n][3] f32 -> [n] f32): queued on the context's stream, never waited for."""
+        sp = shadow_params(filter, strength)
+        self._ck(self.L.vp_volume_shadow_points_device(self.h, C.c_void_p(d_world_xyz), C.c_int64(int(n)), C.byref(sp), C.c_void_p(d_out)),
+                 "vp_volume_shadow_points_device")
+
+    def volume_shadow_image(self, cam, scene_depth=None, filter=abi.VP_SHADOW_BILINEAR, strength=1.0):
+        """vp_volume_shadow_image: the factor per pixel [H, W] for the surfaces of `scene_depth` ([H, W] f32 linear eye depth, 3e38 = nothing;
+        None = the eye depth the library renders from its solids and mesh instances, all 1 without any)."""
+        d = None if scene_depth is None else np.ascontiguousarray(scene_depth, dtype=np.float32)
+        if d is not None and d.shape != (self.H, self.W):
+            raise ValueError("volume_shadow_image(scene_depth): float32 [H, W] expected")
+        out = np.empty((self.H, self.W), dtype=np.float32)
+        sp = shadow_params(filter, strength)
+        self._ck(self.L.vp_volume_shadow_image(self.h, C.byref(cam), None if d is None else _vp(d), C.byref(sp), _vp(out)), "vp_volume_shadow_image")
+        return out
+
+    def volume_shadow_image_device(self, cam, d_scene_depth: int | None, d_out: int, filter=abi.VP_SHADOW_BILINEAR, strength=1.0):
+        """The same on device memory (d_scene_depth 0 / None = the rendered eye depth): queued on the context's stream, never waited for."""
+        sp = shadow_params(filter, strength)
+        self._ck(self.L.vp_volume_shadow_image_device(self.h, C.byref(cam), C.c_void_p(d_scene_depth or 0), C.byref(sp), C.c_void_p(d_out)),
+                 "vp_volume_shadow_image_device")
+
+    def apply_shadow_device(self, d_shadow: int, d_scene: int):
+        """vp_apply_shadow_device: scene.rgb *= shadow on device images ([H][W] f32, [H][W][4] f32), in front of composite_device."""
+        self._ck(self.L.vp_apply_shadow_device(self.h, C.c_void_p(d_shadow), C.c_void_p(d_scene)), "vp_apply_shadow_device")
+
     def set_occluders(self, solids):
         """Boxes (abi.vp_obb) go through vp_set_occluders; any typed solid (abi.vp_occluder: cylinder, ellipsoid) sends the list through vp_set_occluders2."""
         if all(isinstance(b, abi.vp_obb) for b in solids):
@@ -431,6 +474,12 @@ def fit_grid(light_to_world, ls_min, ls_max, num_mv, mv_scale, snap=0.0):
     if rc:
         raise VpfxError("vp_fit_grid", rc, lib().vp_last_error(None).decode())
     return _as_dict(fit)
+
+
+def shadow_params(filter=abi.VP_SHADOW_BILINEAR, strength=1.0) -> abi.vp_shadow_params:
+    sp = abi.vp_shadow_params()
+    sp.filter, sp.strength = int(filter), float(strength)
+    return sp
 
 
 def rigid_inverse(m16) -> np.ndarray:

@@ -54,6 +54,11 @@ class MetavoxelManager:
                                             # two read-back buffers, valid until the call after next), the copy of this frame's image runs beside the
                                             # next frame's bin + fill
         self._async_bufs, self._async_i, self._async_pending = None, 0, False
+        self.castVolumeShadows = False      # CompositeParticles darkens mainSceneRT by the volume's shadow (vp_volume_shadow_image) before the blend
+                                            # (single-GPU contexts: a fan-out context refuses the call with VP_ERR_UNSUPPORTED)
+        self.shadowStrength = 1.0           # vp_shadow_params.strength: 0 = none .. 1 = the light-propagation map's value
+        self.shadowFilter = abi.VP_SHADOW_BILINEAR
+        self._camera = None                 # the camera of the last RenderMetavoxels: the shadow image is projected for the same view
         # ---- scene bindings (dirLight, gridCenter, particleSys, displacement texture)
         self.lightToWorld = np.eye(4, dtype=np.float32).T.reshape(16).copy()
         self.wsGridCenter = np.zeros(3, dtype=np.float32)                       # VPR.cs:138
@@ -133,6 +138,11 @@ class MetavoxelManager:
         """Blit(particlesRT, mainSceneRT, matBlendParticles) (VPR.cs:210; Comp.shader:10: Blend One OneMinusSrcAlpha, One One)."""
         if mainSceneRT is None or self.particlesRT is None:
             return
+        if self.castVolumeShadows and self._camera is not None:
+            # the other half of the effect (FillVolume.shader:224-250's comment): the opaque scene under the smoke loses the light the volume
+            # took.  Same depth source as the ray-march: sceneDepth when the host passes one, else the eye depth the library renders.
+            shadow = self._engine.volume_shadow_image(self._camera, self.sceneDepth, self.shadowFilter, self.shadowStrength)
+            mainSceneRT[..., :3] *= shadow[..., None]
         p = self.particlesRT
         mainSceneRT[..., :3] = p[..., :3] + mainSceneRT[..., :3] * (1.0 - p[..., 3:4])
         mainSceneRT[..., 3] = p[..., 3] + mainSceneRT[..., 3]
@@ -225,6 +235,7 @@ class MetavoxelManager:
 
     def RenderMetavoxels(self, camera):
         rp, keep = self._raymarch_params()
+        self._camera = camera
         if not self.asyncReadback:
             return self._engine.raymarch(camera, rp)
         if self._async_bufs is None:
@@ -331,6 +342,8 @@ class MetavoxelManager:
     def SetFadeOutParticles(self, v): self.fadeOutParticles = bool(v)
     def SetShowMetavoxelDrawOrder(self, v): self.showMetavoxelDrawOrder = bool(v)   # VPR.cs:1096-1099 -> _ShowMetavoxelDrawOrder (:750-754)
     def SetAmbientColor(self, rgb): self.ambientColor = tuple(float(x) for x in rgb)
+    def SetCastVolumeShadows(self, v): self.castVolumeShadows = bool(v)             # added by this binding, like the C# shim's
+    def SetShadowStrength(self, v): self.shadowStrength = min(1.0, max(0.0, float(v)))
 
     @staticmethod
     def MakeCamera(worldToCamera16, cameraToWorld16, position, fieldOfViewDeg, near=0.3, far=1000.0):
